@@ -16,6 +16,13 @@ are independent, so rank r decodes its own 100 k-block shard of one rank-partiti
 (synth.cfg2_shard: weak scaling, no data-path collective); the only collectives are the timing
 barrier, the max-over-ranks reduction of the time and the sum of the bytes / records decoded.
 
+A plain run (`--gpus N --steps K --warmup W`) generates the batch, checks one decode, warms
+up, times the K steps and prints the line.  `--full` adds the legs reported beside the headline:
+the stream-copy ceiling, the CRC-32C verify legs, the batched get, the end-to-end (host in, host
+out) rates and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step decoded
+as DIR/<name>.npy (dump_outputs); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -780,6 +787,41 @@ def run_cfg4(args, dist, world, rank):
     return res
 
 
+def dump_outputs(dirname, out, rank=0, world=1):
+    """--dump-outputs: the arrays a caller of mtblx_decode_blocks receives (include/mtblx.h,
+    mtblx_decoded), as the last timed step left them in `out`, one DIR/<name>.npy each
+    (<name>.rank<r>.npy when world > 1).  Integers are widened to a float type that holds them
+    exactly.  An array longer than its cap is written as a sample: its elements at sorted indices
+    drawn (with replacement) from a generator seeded by the name, so two builds given the same
+    arguments write the same elements.  The caps keep a dump below 64 MB whatever the batch."""
+    import zlib
+    nr, kb, vb, flags = out.totals_host(check=False)
+    nblk = out.nblk
+    u32 = lambda a: a.view(np.uint32)   # noqa: E731  (the library's u32 / u64 outputs in torch's signed types)
+    u64 = lambda a: a.view(np.uint64)   # noqa: E731
+    same = lambda a: a                  # noqa: E731
+    arrays = [  # name, tensor, valid length, host view, dtype written, cap in elements
+        ("status", out.status, nblk, same, np.float32, 500_000),
+        ("nrec", out.nrec, nblk, u32, np.float64, 500_000),
+        ("rec_base", out.rec_base, nblk, u64, np.float64, 500_000),
+        ("key_base", out.key_base, nblk, u64, np.float64, 500_000),
+        ("val_base", out.val_base, nblk, u64, np.float64, 500_000),
+        ("key_end", out.key_end, min(nr, out.rec_cap), u32, np.float64, 1_000_000),
+        ("val_end", out.val_end, min(nr, out.rec_cap), u32, np.float64, 1_000_000),
+        ("keys", out.keys, min(kb, out.keys_cap), same, np.float32, 2_500_000),
+        ("vals", out.vals, min(vb, out.vals_cap), same, np.float32, 2_500_000),
+    ]
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f".rank{rank}.npy" if world > 1 else ".npy"
+    np.save(os.path.join(dirname, "totals" + suffix), np.array([nr, kb, vb, flags], np.float64))
+    for name, t, n, view, dt, cap in arrays:
+        t = t[:n]
+        if n > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, n, cap))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + suffix), view(t.cpu().numpy()).astype(dt))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -788,6 +830,13 @@ def parse_args(argv=None):
                          "multi-rank path (launch, shards, barriers, max-over-ranks) on a 1-GPU box; not scaling")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="cfg2: also run the legs beside the headline figure (stream-copy ceiling, CRC-32C verify, "
+                         "batched get, end-to-end, CPU baseline; each still has its --no-* switch).  Without it the "
+                         "run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="cfg2: after the timed steps, write what the last step decoded (the mtblx_decoded arrays, "
+                         "large ones as a fixed seeded sample) as DIR/<name>.npy")
     ap.add_argument("--blocks", type=int, default=100_000)
     ap.add_argument("--block-size", type=int, default=4096,
                     help="diagnostic: writer block size (cfg2 = 4096; cfg4 also uses 16384 / 65536)")
@@ -835,12 +884,17 @@ def main():
     from mtblx import codec, synth
 
     if args.config in ("cfg3", "cfg4"):
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the cfg2 decode's outputs; not available with --config cfg3 / cfg4")
         res = (run_cfg3 if args.config == "cfg3" else run_cfg4)(args, dist, world, rank)
         if rank == 0:
             print(json.dumps(res), flush=True)
         if dist is not None:
             dist.destroy_process_group()
         return
+
+    if not args.full:   # a plain run: only what the headline figure needs (the other legs: --full)
+        args.no_ceiling = args.no_crc = args.no_get = args.no_e2e = args.no_cpu_baseline = True
 
     t = time.time()
     data, off, ln = synth.cfg2_shard(rank, world, args.blocks, block_size=args.block_size)
@@ -1002,6 +1056,8 @@ def main():
     k_decode_ms = e_start.elapsed_time(e_end) / args.steps
     if out.totals_host() != h:   # the timed launches decoded the same totals
         raise RuntimeError(f"decode totals changed over the timed steps: {out.totals_host()} vs {h}")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     if os.environ.get("MTBLX_BENCH_CHUNKS"):   # diagnostic: per-chunk launch time after the timed region
         cs = []
         for _ in range(int(os.environ["MTBLX_BENCH_CHUNKS"])):

@@ -181,7 +181,7 @@ def test_bench_two_ranks_share_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "3",
-           "--warmup", "1", "--blocks", "20000", "--no-crc", "--no-cpu-baseline"]
+           "--warmup", "1", "--blocks", "20000", "--full", "--no-crc", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=root)
     assert r.returncode == 0, "\n".join(ln for ln in r.stderr.splitlines() if ln.startswith("[rank"))[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
