@@ -155,11 +155,15 @@ struct Decoded {
   std::vector<uint64_t> rec_base, key_base, val_base;
   std::vector<int32_t> status;
   Bytes keys, vals;
+  // decode_batch_positions: offset of every record's value in its block's content (vals stays empty)
+  std::vector<uint32_t> val_pos;
 };
 
-// count -> allocate -> decode -> download, for the batch {data, off, len} on the device
-inline Decoded decode_batch(const uint8_t* d_data, uint64_t data_len, const uint64_t* d_off, const uint32_t* d_len,
-                            uint32_t nblk, uint32_t max_len) {
+// count -> allocate -> decode -> download, for the batch {data, off, len} on the device.
+// positions: mtblx_decode_blocks_valpos -- no value byte is written or downloaded; h.val_pos[r] is
+// where record r's value starts in its block (BlockIter::get's val_offset, src/block.rs:204-213).
+inline Decoded decode_batch_impl(const uint8_t* d_data, uint64_t data_len, const uint64_t* d_off, const uint32_t* d_len,
+                                 uint32_t nblk, uint32_t max_len, bool positions) {
   Decoded h;
   if (nblk == 0) return h;
   mtblx_block_batch in{d_data, data_len, d_off, d_len, nblk, max_len};
@@ -179,17 +183,21 @@ inline Decoded decode_batch(const uint8_t* d_data, uint64_t data_len, const uint
   hip_check(hipDeviceSynchronize(), "sync");
   const auto tot = download<uint64_t>(out.totals, 4);
   launch_check(tot[3], "mtblx_count_blocks");
-  DevBuf ke(4 * tot[0] + 4), ve(4 * tot[0] + 4), kk(tot[1] + 1), vv(tot[2] + 1);
+  DevBuf ke(4 * tot[0] + 4), ve(4 * tot[0] + 4), kk(tot[1] + 1), vv(positions ? 4 * tot[0] + 4 : tot[2] + 1);
   out.key_end = ke.as<uint32_t>();
   out.val_end = ve.as<uint32_t>();
   out.rec_cap = tot[0];
   out.keys = kk.as<uint8_t>();
   out.keys_cap = tot[1];
-  out.vals = vv.as<uint8_t>();
-  out.vals_cap = tot[2];
-  abi_check(mtblx_decode_blocks(&in, &out, ws.p, wsb, nullptr), "mtblx_decode_blocks");
+  if (positions) {
+    abi_check(mtblx_decode_blocks_valpos(&in, &out, vv.as<uint32_t>(), ws.p, wsb, nullptr), "mtblx_decode_blocks_valpos");
+  } else {
+    out.vals = vv.as<uint8_t>();
+    out.vals_cap = tot[2];
+    abi_check(mtblx_decode_blocks(&in, &out, ws.p, wsb, nullptr), "mtblx_decode_blocks");
+  }
   hip_check(hipDeviceSynchronize(), "sync");
-  launch_check(download<uint64_t>(out.totals, 4)[3], "mtblx_decode_blocks");
+  launch_check(download<uint64_t>(out.totals, 4)[3], positions ? "mtblx_decode_blocks_valpos" : "mtblx_decode_blocks");
   h.nrec = download<uint32_t>(out.nrec, nblk);
   h.status = download<int32_t>(out.status, nblk);
   h.rec_base = download<uint64_t>(out.rec_base, nblk);
@@ -198,8 +206,19 @@ inline Decoded decode_batch(const uint8_t* d_data, uint64_t data_len, const uint
   h.key_end = download<uint32_t>(out.key_end, tot[0]);
   h.val_end = download<uint32_t>(out.val_end, tot[0]);
   h.keys = download<uint8_t>(out.keys, tot[1]);
-  h.vals = download<uint8_t>(out.vals, tot[2]);
+  if (positions) h.val_pos = download<uint32_t>(vv.p, tot[0]);
+  else h.vals = download<uint8_t>(out.vals, tot[2]);
   return h;
+}
+inline Decoded decode_batch(const uint8_t* d_data, uint64_t data_len, const uint64_t* d_off, const uint32_t* d_len,
+                            uint32_t nblk, uint32_t max_len) {
+  return decode_batch_impl(d_data, data_len, d_off, d_len, nblk, max_len, false);
+}
+// decode_batch with the values left in the batch: value r of block b is the caller's
+// data[off[b] + val_pos[r] .. + len), len = val_end[r] - (i ? val_end[r-1] : 0)
+inline Decoded decode_batch_positions(const uint8_t* d_data, uint64_t data_len, const uint64_t* d_off,
+                                      const uint32_t* d_len, uint32_t nblk, uint32_t max_len) {
+  return decode_batch_impl(d_data, data_len, d_off, d_len, nblk, max_len, true);
 }
 }  // namespace detail
 

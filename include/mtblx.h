@@ -36,7 +36,9 @@
 extern "C" {
 #endif
 
-#define MTBLX_ABI_VERSION 3   /* 3: the block cut takes a caller-owned workspace (round 6) */
+#define MTBLX_ABI_VERSION 3   /* 3: the block cut takes a caller-owned workspace (round 6).  Still 3 with
+                                 mtblx_decode_blocks_valpos / mtblx_pipe_decode_valpos: two added
+                                 symbols, no existing one changed */
 
 /* ---- API return codes ---- */
 #define MTBLX_OK 0
@@ -123,6 +125,22 @@ size_t mtblx_decode_workspace_bytes(uint32_t nblk);
  * seek_to_first/next/get of src/block.rs for each block; see header comment). */
 int mtblx_decode_blocks(const mtblx_block_batch* in, const mtblx_decoded* out, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* mtblx_decode_blocks without the value bytes: val_pos[r] (device [out->rec_cap]) = offset of
+ * record r's value from the start of its block's content, so the value is
+ *   in->data[blk_off[b] + val_pos[r] .. + len),  len = val_end[r] - (i ? val_end[r-1] : 0)
+ * -- the (val_offset, val_len) BlockIter::get slices with (src/block.rs:204-213), i.e.
+ * decode_entry's p + non_shared (src/block.rs:216-238).  Defined for empty values (the byte
+ * after the key suffix) and for the records a MTBLX_ST_CORRUPT / MTBLX_ST_LOOP block yields
+ * before it stops; val_pos[r] + len <= blk_len[b] - 4 for every record written.
+ * out->vals / out->vals_cap are ignored (may be NULL / 0), never written, never a cause of
+ * MTBLX_ST_OVERFLOW (rec_cap and keys_cap still are; an overflowing block writes no val_pos).
+ * Every other output, totals[2] (value bytes) and val_base included, is exactly what
+ * mtblx_decode_blocks writes.  val_pos == NULL with rec_cap != 0 is MTBLX_E_INVAL.  Same
+ * workspace as mtblx_decode_blocks (the two may alternate on one).  No fused-verify form: run
+ * mtblx_crc32c_blocks on the same stream. */
+int mtblx_decode_blocks_valpos(const mtblx_block_batch* in, const mtblx_decoded* out, uint32_t* val_pos,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* Sizes only (nrec, status, bases, totals); no key/value bytes are written.
  * Lets a caller size `out` exactly before mtblx_decode_blocks. */
@@ -496,6 +514,16 @@ void mtblx_pipe_free(mtblx_pipe* p);
 int mtblx_pipe_decode(mtblx_pipe* p, const uint8_t* file, uint64_t file_len, uint32_t compression,
                       const uint64_t* blk_off, const uint32_t* blk_len, uint32_t nblk, const mtblx_decoded* out,
                       mtblx_pipe_stats* stats);
+/* mtblx_pipe_decode for CompressionType::None with the values left where they are: same
+ * outputs into host `out` except out->vals (ignored, as out->vals_cap), plus val_pos (host
+ * [out->rec_cap], pin it) as mtblx_decode_blocks_valpos defines it.  Positions are
+ * block-relative, so they do not depend on how the file is cut into chunks; value r of block b
+ * is file[blk_off[b] + val_pos[r] ..].  No value byte crosses PCIe back: per record the D2H is
+ * key_end, val_end and val_pos (12 B) plus the key bytes.  One pipe may serve this and
+ * mtblx_pipe_decode alternately.  val_pos == NULL with rec_cap != 0 is MTBLX_E_INVAL. */
+int mtblx_pipe_decode_valpos(mtblx_pipe* p, const uint8_t* file, uint64_t file_len, const uint64_t* blk_off,
+                             const uint32_t* blk_len, uint32_t nblk, const mtblx_decoded* out,
+                             uint32_t* val_pos, mtblx_pipe_stats* stats);
 /* pipe options.  MTBLX_PIPE_DEVICE_SNAPPY (value 1 = on, 0 = off, 2 = auto, the default):
  * snappy files cross PCIe as stored and are decompressed on the device
  * (mtblx_snappy_decompress_dev) right before the decode; off = host decompression in the

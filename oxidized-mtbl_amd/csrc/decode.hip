@@ -207,9 +207,11 @@ __device__ uint32_t gdec32(const uint8_t* d, uint64_t avail, uint32_t& val) {
   return len;
 }
 
-template <bool WRITE>
+// VALPOS (with WRITE): the positions mode (mtblx_decode_blocks_valpos) -- val_pos[r] = block offset
+// of record r's value (decode_entry's p + non_shared) instead of the value bytes; vals is not used.
+template <bool WRITE, bool VALPOS = false>
 __device__ GenOut generic_block(const uint8_t* d, uint64_t L, uint8_t* keys, uint8_t* vals, uint32_t* key_end,
-                                uint32_t* val_end) {
+                                uint32_t* val_end, uint32_t* val_pos = nullptr) {
   GenOut o{0, 0, 0, MTBLX_ST_OK};
   // Block::init (src/block.rs:16-49), release-mode wrapping arithmetic
   if (L < 4) { o.st = MTBLX_ST_INVALID_BLOCK; return o; }
@@ -261,13 +263,20 @@ __device__ GenOut generic_block(const uint8_t* d, uint64_t L, uint8_t* keys, uin
       if (m) { MTBLX_CHK(ks, m); }
       if (newlen) { MTBLX_CHK(kd, newlen); }
       if (ns) { MTBLX_CHK(d + p, ns); }
-      if (vl) { MTBLX_CHK(d + p + ns, vl); MTBLX_CHK(vals + o.vb, vl); }
+      if constexpr (!VALPOS) {
+        if (vl) { MTBLX_CHK(d + p + ns, vl); MTBLX_CHK(vals + o.vb, vl); }
+      }
       MTBLX_CHK(key_end + o.nrec, 4);
       MTBLX_CHK(val_end + o.nrec, 4);
       for (uint64_t i = 0; i < m; ++i) kd[i] = ks[i];
       for (uint64_t i = 0; i < ns; ++i) kd[m + i] = d[p + i];
-      uint8_t* vd = vals + o.vb;
-      for (uint64_t i = 0; i < vl; ++i) vd[i] = d[p + ns + i];
+      if constexpr (VALPOS) {
+        MTBLX_CHK(val_pos + o.nrec, 4);
+        val_pos[o.nrec] = (uint32_t)(p + ns);
+      } else {
+        uint8_t* vd = vals + o.vb;
+        for (uint64_t i = 0; i < vl; ++i) vd[i] = d[p + ns + i];
+      }
       key_end[o.nrec] = (uint32_t)(o.kb + newlen);
       val_end[o.nrec] = (uint32_t)(o.vb + vl);
     }
@@ -325,6 +334,7 @@ struct TileCfg {
   static constexpr int MAXINT = MAXINT_;  // restart intervals per tile (<= kThreads)
   static constexpr int MAXBLK = MAXBLK_;  // blocks per tile (<= 64)
   static constexpr bool PREFETCH = PREFETCH_;
+  static constexpr bool VALPOS = false;   // positions mode: val_pos instead of value bytes (CfgLargeP)
 };
 
 // per-record metadata, 16 bytes: one ds_write_b128 / ds_read_b128
@@ -401,6 +411,7 @@ struct TileArgs {
   uint32_t flags_direct;       // k_decode_pipe: flags go straight to totals[3] (pipe_zero_flags)
   uint64_t wait_ticks;         // WaitBound's limit (kWaitTicks; MTBLX_DEBUG_WAIT_MS shortens it)
   uint64_t dbg_delay0;         // debug: workgroup 0 starts this many ticks late (MTBLX_DEBUG_DELAY0_MS)
+  uint32_t* val_pos;           // VALPOS kernels: [rec_cap] block offset of every record's value
 };
 
 // Workspace header (byte 128 of the workspace).  The workspace carries state from call to
@@ -1098,6 +1109,10 @@ __global__ void __launch_bounds__(kThreads, C::MINW) k_decode_tiles(TileArgs a) 
         MTBLX_CHK(a.val_end + gr, 4);
         a.key_end[gr] = ks + klen - S.bkbb[j];
         a.val_end[gr] = vs + vl - S.bvbb[j];
+        if constexpr (C::VALPOS) {
+          MTBLX_CHK(a.val_pos + gr, 4);
+          a.val_pos[gr] = pos + ns;   // block offset of the value: no value bytes move
+        } else {
 #ifndef MTBLX_ABL_NOVAL
         // value bytes: LDS window -> unaligned 16-byte stores
         const uint32_t vsrc = bo + pos + ns;
@@ -1108,6 +1123,7 @@ __global__ void __launch_bounds__(kThreads, C::MINW) k_decode_tiles(TileArgs a) 
           store_bytes(vd + o, w4, m < 16 ? m : 16);
         }
 #endif
+        }
 #ifndef MTBLX_ABL_NOKEY
         // key bytes: each byte comes from the suffix of the latest record s <= q (same
         // interval) with shared_s <= byte index
@@ -1147,8 +1163,12 @@ __global__ void __launch_bounds__(kThreads, C::MINW) k_decode_tiles(TileArgs a) 
     if (tid < (int)nb && !S.bok[tid] && S.bwr[tid]) {
       const uint32_t j = tid, bo = S.boff[j], L = S.blen[j];
       const uint8_t* d = (bo != kNotStaged) ? (S.stage + bo) : (a.data + a.blk_off[b0 + j]);
-      generic_block<true>(d, L, a.keys + pk + S.bkbb[j], a.vals + pv + S.bvbb[j], a.key_end + pr + S.brb[j],
-                          a.val_end + pr + S.brb[j]);
+      if constexpr (C::VALPOS)
+        generic_block<true, true>(d, L, a.keys + pk + S.bkbb[j], nullptr, a.key_end + pr + S.brb[j],
+                                  a.val_end + pr + S.brb[j], a.val_pos + pr + S.brb[j]);
+      else
+        generic_block<true>(d, L, a.keys + pk + S.bkbb[j], a.vals + pv + S.bvbb[j], a.key_end + pr + S.brb[j],
+                            a.val_end + pr + S.brb[j]);
     }
     __syncthreads();
   }
@@ -1233,6 +1253,7 @@ struct PipeCfg {
   static constexpr int COPY0 = kPipeLoadWave + LOADW;             // first copy wave
   static constexpr int NCOPY = kPipeThreads / kWave - COPY0;      // copy waves
   static constexpr int ROWS = NCOPY * (kWave / 16);               // intervals per copy round
+  static constexpr bool VALPOS = false;   // positions mode: val_pos instead of value bytes (PipeSmallP / PipeLargeP)
 };
 // (PipeLarge with four loaders and ten copy waves: +0.8 % on 16 B keys, -16 % on cfg3's long
 // Zipf keys, whose copy is the longer half of the iteration)
@@ -1249,6 +1270,11 @@ using PipeSmall = PipeCfg<MTBLX_SMALL_TB, 3, 16, 56>;   // blocks up to ~48 KiB 
 using PipeLarge = PipeCfg<65664, 2, 2, 64, false, MTBLX_LARGE_LOADW>;    // blocks up to ~64 KiB (cfg3, cfg4 64 KiB)
 using PipeSmallV = PipeCfg<49152, 3, 16, 56, true>;
 using PipeLargeV = PipeCfg<65664, 2, 2, 64, true>;
+// Positions twins (mtblx_decode_blocks_valpos): the same pipeline, but the copy waves store each
+// record's value offset in its block (4 B) instead of the value bytes.  Derived, so the plain
+// kernels' names and code stay what they are; the fused-verify kernels get no twin.
+struct PipeSmallP : PipeSmall { static constexpr bool VALPOS = true; };
+struct PipeLargeP : PipeLarge { static constexpr bool VALPOS = true; };
 
 template <class P>
 struct alignas(16) PipeBuf {
@@ -1964,7 +1990,9 @@ __device__ __forceinline__ void copy_emit(const PipeBuf<P>& B, const TileArgs& a
     const uint64_t gr = pr + B.icnt[r.f] + r.k;
     ost(a.key_end + gr, r.ks + r.klen - B.bkbb[r.j]);
     ost(a.val_end + gr, r.vs + r.vl - B.bvbb[r.j]);
+    if constexpr (P::VALPOS) ost(a.val_pos + gr, r.sp + r.ns - r.bo);   // block offset of the value
   }
+  if constexpr (!P::VALPOS) {
 #ifndef MTBLX_ABL_NOVAL
   // values.  Fast path (wave-uniform): every live entry of this round has the same value
   // length U, a multiple of 16 -> lane k of a row writes 16 B chunks k, k+16, ... of the
@@ -2014,6 +2042,7 @@ __device__ __forceinline__ void copy_emit(const PipeBuf<P>& B, const TileArgs& a
     }
   }
 #endif
+  }
 #ifndef MTBLX_ABL_NOKEY
   uint8_t* kd = a.keys + pk + r.ks;
   if (live && r.klen > 0u) store_bytes(kd, r.W0, r.klen < 16u ? r.klen : 16u);
@@ -2091,8 +2120,12 @@ __device__ __forceinline__ void pipe_copy(const PipeBuf<P>& B, const TileArgs& a
     const uint64_t pr = B.tpre[0], pk = B.tpre[1], pv = B.tpre[2];
     const uint32_t j = ct, bo = B.boff[j], L = B.blen[j];
     const uint8_t* d = (bo != kNotStaged) ? (B.stage + bo) : (a.data + a.blk_off[B.b0 + j]);
-    generic_block<true>(d, L, a.keys + pk + B.bkbb[j], a.vals + pv + B.bvbb[j], a.key_end + pr + B.brb[j],
-                        a.val_end + pr + B.brb[j]);
+    if constexpr (P::VALPOS)
+      generic_block<true, true>(d, L, a.keys + pk + B.bkbb[j], nullptr, a.key_end + pr + B.brb[j],
+                                a.val_end + pr + B.brb[j], a.val_pos + pr + B.brb[j]);
+    else
+      generic_block<true>(d, L, a.keys + pk + B.bkbb[j], a.vals + pv + B.bvbb[j], a.key_end + pr + B.brb[j],
+                          a.val_end + pr + B.brb[j]);
   }
 }
 
@@ -2739,6 +2772,7 @@ __global__ void __launch_bounds__(kPipeThreads, 1) k_decode_pipe(TileArgs a) {
 
 using CfgSmall = TileCfg<32768, 640, 256, 64, true, 3>;
 using CfgLarge = TileCfg<67584, 1024, 256, 16, false, 1>;
+struct CfgLargeP : CfgLarge { static constexpr bool VALPOS = true; };   // positions twin (see PipeSmallP)
 
 }  // namespace mtblx
 
@@ -2844,8 +2878,14 @@ static uint64_t debug_ms(const char* name, uint64_t dflt) {
   return e ? strtoull(e, nullptr, 0) * 100000ull : dflt;   // s_memrealtime: 100 MHz
 }
 
-extern "C" int mtblx_impl_run(const mtblx_block_batch* in, const mtblx_decoded* out, void* ws, size_t ws_bytes,
-                              int write, hipStream_t s, int verify, uint32_t* crc, uint8_t* crc_bad, int framed) {
+// positions: the mode of mtblx_decode_blocks_valpos (the ...P kernels; no verify twin).  Value bytes
+// cannot overflow there: the kernels see vals = NULL and an unbounded vals_cap.
+static int run_decode(const mtblx_block_batch* in, const mtblx_decoded* out_, void* ws, size_t ws_bytes, int write,
+                      hipStream_t s, int verify, uint32_t* crc, uint8_t* crc_bad, int framed, bool positions,
+                      uint32_t* val_pos) {
+  mtblx_decoded outv = *out_;
+  if (positions) { outv.vals = nullptr; outv.vals_cap = ~0ull; }
+  const mtblx_decoded* out = &outv;
   const uint32_t nblk = in->nblk;
   const uint64_t cap64 = ws_bytes > 320u ? (ws_bytes - 320u) / (8u * kTileWords) : 0u;
   const uint32_t wscap = cap64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap64;
@@ -2860,13 +2900,22 @@ extern "C" int mtblx_impl_run(const mtblx_block_batch* in, const mtblx_decoded* 
              wscap,        0,             0,            debug_flags()};
   a.wait_ticks = debug_ms("MTBLX_DEBUG_WAIT_MS", kWaitTicks);
   a.dbg_delay0 = debug_ms("MTBLX_DEBUG_DELAY0_MS", 0);
+  a.val_pos = val_pos;
 #define MTBLX_DECODE_PTRS                                                                                        \
   (MTBLX_R(in->data, in->data_len), MTBLX_R(in->blk_off, 8ull * nblk), MTBLX_R(in->blk_len, 4ull * nblk),         \
    MTBLX_R(out->nrec, 4ull * nblk), MTBLX_R(out->rec_base, 8ull * nblk), MTBLX_R(out->key_base, 8ull * nblk),      \
    MTBLX_R(out->val_base, 8ull * nblk), MTBLX_R(out->status, 4ull * nblk), MTBLX_R(out->key_end, 4 * out->rec_cap), \
    MTBLX_R(out->val_end, 4 * out->rec_cap), MTBLX_R(out->keys, out->keys_cap), MTBLX_R(out->vals, out->vals_cap),   \
-   MTBLX_R(out->totals, 32), MTBLX_R(ws, ws_bytes), MTBLX_R(crc, 4ull * nblk), MTBLX_R(crc_bad, nblk))
-  if (p.kind == 0) {
+   MTBLX_R(out->totals, 32), MTBLX_R(ws, ws_bytes), MTBLX_R(crc, 4ull * nblk), MTBLX_R(crc_bad, nblk),          \
+   MTBLX_R(val_pos, 4 * out->rec_cap))
+  if (positions) {
+    if (p.kind == 0)
+      MTBLX_LAUNCH(MTBLX_DECODE_PTRS, k_decode_pipe<PipeSmallP>, dim3(pipe_grid(p.ntiles)), dim3(kPipeThreads), 0, s, a);
+    else if (p.kind == 1)
+      MTBLX_LAUNCH(MTBLX_DECODE_PTRS, k_decode_pipe<PipeLargeP>, dim3(pipe_grid(p.ntiles)), dim3(kPipeThreads), 0, s, a);
+    else
+      MTBLX_LAUNCH(MTBLX_DECODE_PTRS, k_decode_tiles<CfgLargeP>, dim3(resident_grid<CfgLargeP>(p.ntiles)), dim3(kThreads), 0, s, a);
+  } else if (p.kind == 0) {
     if (verify)
       MTBLX_LAUNCH(MTBLX_DECODE_PTRS, k_decode_pipe<PipeSmallV>, dim3(pipe_grid(p.ntiles)), dim3(kPipeThreads), 0, s, a);
     else
@@ -2882,4 +2931,14 @@ extern "C" int mtblx_impl_run(const mtblx_block_batch* in, const mtblx_decoded* 
     if (verify && hipGetLastError() == hipSuccess) return mtblx_crc32c_blocks(in, crc, crc_bad, framed, s);
   }
   return hipGetLastError() == hipSuccess ? MTBLX_OK : MTBLX_E_HIP;
+}
+
+extern "C" int mtblx_impl_run(const mtblx_block_batch* in, const mtblx_decoded* out, void* ws, size_t ws_bytes,
+                              int write, hipStream_t s, int verify, uint32_t* crc, uint8_t* crc_bad, int framed) {
+  return run_decode(in, out, ws, ws_bytes, write, s, verify, crc, crc_bad, framed, false, nullptr);
+}
+
+extern "C" int mtblx_impl_run_valpos(const mtblx_block_batch* in, const mtblx_decoded* out, uint32_t* val_pos, void* ws,
+                                     size_t ws_bytes, hipStream_t s) {
+  return run_decode(in, out, ws, ws_bytes, 1, s, 0, nullptr, nullptr, 0, true, val_pos);
 }

@@ -14,6 +14,8 @@ extern "C" int mtblx_impl_run(const mtblx_block_batch* in, const mtblx_decoded* 
 
 extern "C" int mtblx_crc32c_blocks(const mtblx_block_batch* in, uint32_t* crc, uint8_t* bad, int framed,
                                    void* stream);
+extern "C" int mtblx_impl_run_valpos(const mtblx_block_batch* in, const mtblx_decoded* out, uint32_t* val_pos, void* ws,
+                                     size_t ws_bytes, hipStream_t s);
 
 extern "C" int mtblx_abi_version(void) { return MTBLX_ABI_VERSION; }
 
@@ -70,6 +72,17 @@ extern "C" int mtblx_decode_blocks(const mtblx_block_batch* in, const mtblx_deco
       (!out->val_end && out->rec_cap))
     return MTBLX_E_INVAL;
   return mtblx_impl_run(in, out, ws, wsb, 1, reinterpret_cast<hipStream_t>(stream), 0, nullptr, nullptr, 0);
+}
+
+extern "C" int mtblx_decode_blocks_valpos(const mtblx_block_batch* in, const mtblx_decoded* out, uint32_t* val_pos,
+                                          void* ws, size_t wsb, void* stream) {
+  if (out && !val_pos && out->rec_cap) return MTBLX_E_INVAL;   // before any HIP call
+  int c = check_common(in, out, ws, wsb, stream);
+  if (c != 1) return c;
+  // out->vals / out->vals_cap are not looked at: no value byte is written
+  if ((!out->keys && out->keys_cap) || (!out->key_end && out->rec_cap) || (!out->val_end && out->rec_cap))
+    return MTBLX_E_INVAL;
+  return mtblx_impl_run_valpos(in, out, val_pos, ws, wsb, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int mtblx_decode_blocks_verify(const mtblx_block_batch* in, const mtblx_decoded* out, uint32_t* crc,

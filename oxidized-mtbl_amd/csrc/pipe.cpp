@@ -135,6 +135,9 @@ struct Slot {
   uint8_t* dz = nullptr;      // device snappy: dec_len u32[blocks] | status i32[blocks]
   int32_t* hz = nullptr;      // device snappy: pinned copy of the status
   uint8_t* dout = nullptr;    // device outputs
+  uint32_t* vpos = nullptr;   // positions mode: val_pos u32[cap.rec] in the tail region, which then holds no vals
+  uint64_t tail = 0;          // bytes of the tail region of dout (vals, or val_pos)
+  bool positions = false;     // the mode dout is laid out for
   uint64_t* htot = nullptr;   // pinned chunk totals [4]
   Caps cap;
   mtblx_decoded o{};
@@ -186,7 +189,15 @@ void free_outputs(Slot& s) {
   s.dout = nullptr;
 }
 
-int alloc_outputs(Slot& s, const Caps& c) {
+// the tail region of dout serves the mode: the value bytes, or (positions) one u32 per record
+void point_tail(Slot& s, uint8_t* tail_at, bool positions) {
+  s.positions = positions;
+  s.vpos = positions ? reinterpret_cast<uint32_t*>(tail_at) : nullptr;
+  s.o.vals = positions ? nullptr : tail_at;
+  s.o.vals_cap = s.cap.vals = positions ? 0 : s.tail;
+}
+
+int alloc_outputs(Slot& s, const Caps& c, bool positions) {
   free_outputs(s);
   uint64_t off = 0;
   auto take = [&](uint64_t n) {
@@ -196,7 +207,9 @@ int alloc_outputs(Slot& s, const Caps& c) {
   };
   const uint64_t o_nrec = take(4 * c.blocks), o_st = take(4 * c.blocks), o_rb = take(8 * c.blocks),
                  o_kb = take(8 * c.blocks), o_vb = take(8 * c.blocks), o_tot = take(32), o_ke = take(4 * c.rec),
-                 o_ve = take(4 * c.rec), o_k = take(c.keys), o_v = take(c.vals);
+                 o_ve = take(4 * c.rec), o_k = take(c.keys);
+  s.tail = positions ? 4 * c.rec : c.vals;
+  const uint64_t o_v = take(s.tail);
   if (hipMalloc(&s.dout, off) != hipSuccess) return MTBLX_E_HIP;
   uint8_t* b = s.dout;
   s.o.nrec = reinterpret_cast<uint32_t*>(b + o_nrec);
@@ -208,13 +221,23 @@ int alloc_outputs(Slot& s, const Caps& c) {
   s.o.key_end = reinterpret_cast<uint32_t*>(b + o_ke);
   s.o.val_end = reinterpret_cast<uint32_t*>(b + o_ve);
   s.o.keys = b + o_k;
-  s.o.vals = b + o_v;
   s.o.rec_cap = c.rec;
   s.o.keys_cap = c.keys;
-  s.o.vals_cap = c.vals;
   s.cap.rec = c.rec;
   s.cap.keys = c.keys;
-  s.cap.vals = c.vals;
+  point_tail(s, b + o_v, positions);
+  return MTBLX_OK;
+}
+
+// A slot laid out by a call of the other mode: its tail region is re-used where it is large
+// enough for this mode, else the outputs are allocated again.  (The streams are idle.)
+int set_mode(Slot& s, bool positions) {
+  if (s.positions == positions) return MTBLX_OK;
+  Caps c = s.cap;
+  c.vals = caps_for(s.cap.in, s.cap.blocks).vals;
+  uint8_t* tail_at = s.positions ? reinterpret_cast<uint8_t*>(s.vpos) : s.o.vals;
+  if (s.tail < (positions ? 4 * c.rec : c.vals)) return alloc_outputs(s, c, positions);
+  point_tail(s, tail_at, positions);
   return MTBLX_OK;
 }
 
@@ -245,7 +268,7 @@ int alloc_slot(Slot& s, const Caps& c) {
   if (hipEventCreateWithFlags(&s.e_h2d, hipEventDisableTiming) != hipSuccess) return MTBLX_E_HIP;
   if (hipEventCreateWithFlags(&s.e_d2h, hipEventDisableTiming) != hipSuccess) return MTBLX_E_HIP;
   if (hipEventCreate(&s.e_dec0) != hipSuccess || hipEventCreate(&s.e_dec) != hipSuccess) return MTBLX_E_HIP;
-  return alloc_outputs(s, c);
+  return alloc_outputs(s, c, false);
 }
 
 bool host_pinned(const void* p) {
@@ -291,9 +314,11 @@ extern "C" void mtblx_pipe_free(mtblx_pipe* p) {
   delete p;
 }
 
-extern "C" int mtblx_pipe_decode(mtblx_pipe* p, const uint8_t* file, uint64_t file_len, uint32_t compression,
-                                 const uint64_t* blk_off, const uint32_t* blk_len, uint32_t nblk,
-                                 const mtblx_decoded* out, mtblx_pipe_stats* stats) {
+// positions: the mode of mtblx_pipe_decode_valpos (compression == 0) -- every chunk is decoded
+// with mtblx_decode_blocks_valpos and its val_pos comes back instead of its vals.
+static int pipe_run(mtblx_pipe* p, const uint8_t* file, uint64_t file_len, uint32_t compression,
+                    const uint64_t* blk_off, const uint32_t* blk_len, uint32_t nblk, const mtblx_decoded* out,
+                    bool positions, uint32_t* val_pos, mtblx_pipe_stats* stats) {
   if (!p || !out || (nblk && (!file || !blk_off || !blk_len)) || compression > 5) return MTBLX_E_INVAL;
   if (nblk && (!out->nrec || !out->rec_base || !out->key_base || !out->val_base || !out->status || !out->totals))
     return MTBLX_E_INVAL;
@@ -395,7 +420,13 @@ extern "C" int mtblx_pipe_decode(mtblx_pipe* p, const uint8_t* file, uint64_t fi
     for (auto& s : p->slot)
       if (alloc_slot(s, c) != MTBLX_OK) return MTBLX_E_HIP;
   }
+  for (auto& s : p->slot)
+    if (set_mode(s, positions) != MTBLX_OK) return MTBLX_E_HIP;
   const bool pinned_src = ranged && nblk && host_pinned(file);
+  auto decode = [&](const mtblx_block_batch& in, Slot& s, hipStream_t sd) {
+    return positions ? mtblx_decode_blocks_valpos(&in, &s.o, s.vpos, p->ws, p->ws_bytes, sd)
+                     : mtblx_decode_blocks(&in, &s.o, p->ws, p->ws_bytes, sd);
+  };
 
   uint64_t R = 0, K = 0, V = 0, flags = 0;
   std::vector<std::pair<uint32_t, uint32_t>> skipped;   // chunks whose outputs did not fit `out`
@@ -491,7 +522,7 @@ extern "C" int mtblx_pipe_decode(mtblx_pipe* p, const uint8_t* file, uint64_t fi
       if (hipMemcpyAsync(s.hz, zst, 4ull * c.nb, hipMemcpyDeviceToHost, sd) != hipSuccess) return MTBLX_E_HIP;
       in = mtblx_block_batch{s.du, std::max<uint64_t>(ubytes, 1), d_zoff, dec_len, c.nb, c.maxlen};
     }
-    int r = mtblx_decode_blocks(&in, &s.o, p->ws, p->ws_bytes, sd);
+    int r = decode(in, s, sd);
     if (r != MTBLX_OK) return r;
     if (hipMemcpyAsync(s.htot, s.o.totals, 32, hipMemcpyDeviceToHost, sd) != hipSuccess) return MTBLX_E_HIP;
     if (hipEventRecord(s.e_dec, sd) != hipSuccess) return MTBLX_E_HIP;
@@ -523,7 +554,7 @@ extern "C" int mtblx_pipe_decode(mtblx_pipe* p, const uint8_t* file, uint64_t fi
         c2.vals = std::max(c2.vals, vb + 64);
       }
       const bool grow = (s.htot[3] & 1ull) != 0;
-      if (hipStreamSynchronize(p->s_d2h) != hipSuccess || (grow && alloc_outputs(s, c2) != MTBLX_OK))
+      if (hipStreamSynchronize(p->s_d2h) != hipSuccess || (grow && alloc_outputs(s, c2, positions) != MTBLX_OK))
         return MTBLX_E_HIP;
       mtblx_block_batch in{s.d + s.data_at(), std::max<uint64_t>(compression == 0 ? c.hi - c.lo : c.ubytes, 1),
                            reinterpret_cast<const uint64_t*>(s.d),
@@ -531,7 +562,7 @@ extern "C" int mtblx_pipe_decode(mtblx_pipe* p, const uint8_t* file, uint64_t fi
       if (dz_mode)
         in = mtblx_block_batch{s.du, s.du_bytes(), reinterpret_cast<const uint64_t*>(s.d + s.dir_bytes()),
                                reinterpret_cast<const uint32_t*>(s.dz), c.nb, c.maxlen};
-      int r = mtblx_decode_blocks(&in, &s.o, p->ws, p->ws_bytes, p->s_dec);
+      int r = decode(in, s, p->s_dec);
       if (r != MTBLX_OK) return r;
       if (hipMemcpyAsync(s.htot, s.o.totals, 32, hipMemcpyDeviceToHost, p->s_dec) != hipSuccess ||
           hipEventRecord(s.e_dec, p->s_dec) != hipSuccess || hipEventSynchronize(s.e_dec) != hipSuccess)
@@ -544,8 +575,9 @@ extern "C" int mtblx_pipe_decode(mtblx_pipe* p, const uint8_t* file, uint64_t fi
     flags |= s.htot[3] & ~1ull;
     hipStream_t so = p->s_d2h;
     if (hipStreamWaitEvent(so, s.e_dec, 0) != hipSuccess) return MTBLX_E_HIP;
-    const bool fits = R + nr <= out->rec_cap && K + kb <= out->keys_cap && V + vb <= out->vals_cap &&
-                      (!nr || (out->key_end && out->val_end)) && (!kb || out->keys) && (!vb || out->vals);
+    const bool fits = R + nr <= out->rec_cap && K + kb <= out->keys_cap &&
+                      (!nr || (out->key_end && out->val_end)) && (!kb || out->keys) &&
+                      (positions || (V + vb <= out->vals_cap && (!vb || out->vals)));
     MTBLX_LAUNCH((s.o.rec_base, s.o.key_base, s.o.val_base), k_rebase, dim3((c.nb + 255) / 256), dim3(256), 0, so, s.o.rec_base, s.o.key_base, s.o.val_base,
                        c.nb, R, K, V);
     auto d2h = [&](void* dst, const void* srcp, uint64_t n) {
@@ -558,7 +590,8 @@ extern "C" int mtblx_pipe_decode(mtblx_pipe* p, const uint8_t* file, uint64_t fi
               d2h(out->val_base + c.b0, s.o.val_base, 8ull * c.nb);
     if (fits) {
       ok = ok && d2h(out->key_end + R, s.o.key_end, 4 * nr) && d2h(out->val_end + R, s.o.val_end, 4 * nr) &&
-           d2h(out->keys + K, s.o.keys, kb) && d2h(out->vals + V, s.o.vals, vb);
+           d2h(out->keys + K, s.o.keys, kb) &&
+           (positions ? d2h(val_pos + R, s.vpos, 4 * nr) : d2h(out->vals + V, s.o.vals, vb));
     } else {
       skipped.emplace_back(c.b0, c.nb);
       flags |= 1ull;
@@ -596,6 +629,19 @@ extern "C" int mtblx_pipe_decode(mtblx_pipe* p, const uint8_t* file, uint64_t fi
   st.seconds = now_s() - t_start;
   if (stats) *stats = st;
   return MTBLX_OK;
+}
+
+extern "C" int mtblx_pipe_decode(mtblx_pipe* p, const uint8_t* file, uint64_t file_len, uint32_t compression,
+                                 const uint64_t* blk_off, const uint32_t* blk_len, uint32_t nblk,
+                                 const mtblx_decoded* out, mtblx_pipe_stats* stats) {
+  return pipe_run(p, file, file_len, compression, blk_off, blk_len, nblk, out, false, nullptr, stats);
+}
+
+extern "C" int mtblx_pipe_decode_valpos(mtblx_pipe* p, const uint8_t* file, uint64_t file_len, const uint64_t* blk_off,
+                                        const uint32_t* blk_len, uint32_t nblk, const mtblx_decoded* out,
+                                        uint32_t* val_pos, mtblx_pipe_stats* stats) {
+  if (!out || (!val_pos && out->rec_cap)) return MTBLX_E_INVAL;
+  return pipe_run(p, file, file_len, 0, blk_off, blk_len, nblk, out, true, val_pos, stats);
 }
 
 extern "C" int mtblx_pipe_set(mtblx_pipe* p, int option, int64_t value) {

@@ -29,12 +29,12 @@ EMIT_END, EMIT_PANIC, EMIT_LOOP, EMIT_MAX, EMIT_OVERFLOW = range(5)
 # every symbol the public headers declare (checked by tests/test_abi.py)
 EXPORTS = [
     "mtblx_abi_version", "mtblx_device_ok", "mtblx_decode_workspace_bytes", "mtblx_decode_blocks",
-    "mtblx_count_blocks", "mtblx_decode_counted", "mtblx_decode_blocks_verify", "mtblx_crc32c_blocks", "mtblx_block_dir", "mtblx_get", "mtblx_get_decompressed", "mtblx_crc32c", "mtblx_varint_decode64", "mtblx_read_footer", "mtblx_frame_block",
+    "mtblx_count_blocks", "mtblx_decode_counted", "mtblx_decode_blocks_valpos", "mtblx_decode_blocks_verify", "mtblx_crc32c_blocks", "mtblx_block_dir", "mtblx_get", "mtblx_get_decompressed", "mtblx_crc32c", "mtblx_varint_decode64", "mtblx_read_footer", "mtblx_frame_block",
     "mtblx_writer_new", "mtblx_writer_insert", "mtblx_writer_insert_batch", "mtblx_writer_finish",
     "mtblx_writer_block_count", "mtblx_writer_block_dir", "mtblx_writer_free", "mtblx_free",
     "mtblx_snappy_max_compressed_len", "mtblx_snappy_uncompressed_len", "mtblx_snappy_decompress",
     "mtblx_snappy_compress", "mtblx_snappy_decompress_blocks", "mtblx_pipe_new", "mtblx_pipe_free",
-    "mtblx_pipe_decode", "mtblx_pipe_set", "mtblx_host_alloc", "mtblx_host_free", "mtblx_host_register", "mtblx_host_unregister",
+    "mtblx_pipe_decode", "mtblx_pipe_decode_valpos", "mtblx_pipe_set", "mtblx_host_alloc", "mtblx_host_free", "mtblx_host_register", "mtblx_host_unregister",
     "mtblx_encode_plan", "mtblx_encode_workspace_bytes", "mtblx_encode_blocks", "mtblx_plan_keep_bytes",
     "mtblx_encode_plan_keep", "mtblx_encode_blocks_planned", "mtblx_plan_release", "mtblx_plan_workspace_bytes",
     "mtblx_plan_serial_workspace_bytes",
@@ -111,6 +111,9 @@ def lib() -> C.CDLL:
         for f in (L.mtblx_decode_blocks, L.mtblx_count_blocks, L.mtblx_decode_counted):
             f.argtypes = [C.POINTER(BlockBatch), C.POINTER(Decoded), C.c_void_p, C.c_size_t, C.c_void_p]
             f.restype = C.c_int
+        L.mtblx_decode_blocks_valpos.argtypes = [C.POINTER(BlockBatch), C.POINTER(Decoded), C.c_void_p, C.c_void_p,
+                                                 C.c_size_t, C.c_void_p]
+        L.mtblx_decode_blocks_valpos.restype = C.c_int
         L.mtblx_decode_blocks_verify.argtypes = [C.POINTER(BlockBatch), C.POINTER(Decoded), C.c_void_p, C.c_void_p,
                                                  C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         L.mtblx_decode_blocks_verify.restype = C.c_int
@@ -166,6 +169,9 @@ def lib() -> C.CDLL:
         L.mtblx_pipe_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.c_uint32, C.POINTER(Decoded), C.POINTER(PipeStats)]
         L.mtblx_pipe_decode.restype = C.c_int
+        L.mtblx_pipe_decode_valpos.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                               C.POINTER(Decoded), C.c_void_p, C.POINTER(PipeStats)]
+        L.mtblx_pipe_decode_valpos.restype = C.c_int
         L.mtblx_pipe_set.argtypes = [C.c_void_p, C.c_int, C.c_int64]
         L.mtblx_pipe_set.restype = C.c_int
         L.mtblx_encode_plan.argtypes = [C.POINTER(Records), C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,

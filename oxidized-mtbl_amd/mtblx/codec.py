@@ -79,7 +79,9 @@ class DeviceBatch:
 class DecodedBlocks:
     """Device outputs in the layout of include/mtblx.h (mtblx_decoded)."""
 
-    def __init__(self, nblk: int, rec_cap: int, keys_cap: int, vals_cap: int, device="cuda"):
+    def __init__(self, nblk: int, rec_cap: int, keys_cap: int, vals_cap: int, device="cuda", values: bool = True):
+        """values=False (with vals_cap=0): no value buffer at all -- `vals` is NULL in the C
+        struct, as decode_positions_into allows."""
         z = lambda n, dt: torch.zeros(max(int(n), 1), dtype=dt, device=device)  # noqa: E731
         self.nblk = nblk
         self.nrec = z(nblk, torch.int32)
@@ -90,7 +92,9 @@ class DecodedBlocks:
         self.key_end = z(rec_cap, torch.int32)
         self.val_end = z(rec_cap, torch.int32)
         self.keys = z(keys_cap, torch.uint8)
-        self.vals = z(vals_cap, torch.uint8)
+        if not values and vals_cap:
+            raise ValueError("values=False needs vals_cap=0")
+        self.vals = z(vals_cap, torch.uint8) if values else torch.empty(0, dtype=torch.uint8, device=device)
         self.totals = z(4, torch.int64)
         self.rec_cap, self.keys_cap, self.vals_cap = int(rec_cap), int(keys_cap), int(vals_cap)
 
@@ -213,6 +217,43 @@ def decode_into(batch: DeviceBatch, out: DecodedBlocks, ws: Workspace, stream=No
     ws._launched(stream, h)
     if rc != 0:
         raise RuntimeError(f"mtblx_decode_blocks failed: {rc}")
+
+
+def decode_positions_into(batch: DeviceBatch, out: DecodedBlocks, val_pos: torch.Tensor, ws: Workspace,
+                          stream=None) -> None:
+    """decode_into without the value bytes (mtblx_decode_blocks_valpos): val_pos (int32 [rec_cap],
+    device) receives, per record, the offset of its value from the start of its block's content;
+    out.vals / out.vals_cap are ignored and never written.  Value r of block b is
+    batch.data[blk_off[b] + val_pos[r] : ... + len], len from val_end as in HostDecoded.records."""
+    L = _require_device()
+    if val_pos is not None and val_pos.numel() < out.rec_cap:
+        raise ValueError("val_pos holds fewer than rec_cap records")
+    b, o = batch.cstruct(), out.cstruct()
+    h = ws._claim(stream)
+    rc = L.mtblx_decode_blocks_valpos(C.byref(b), C.byref(o), C.c_void_p(_u(val_pos)),
+                                      C.c_void_p(ws.buf.data_ptr()), ws.nbytes, C.c_void_p(h))
+    ws._launched(stream, h)
+    if rc != 0:
+        raise RuntimeError(f"mtblx_decode_blocks_valpos failed: {rc}")
+
+
+def decode_positions(batch: DeviceBatch, stream=None):
+    """Size exactly (count pass), allocate, decode positions -> (DecodedBlocks without a value
+    buffer, val_pos int32 tensor [records]).  Synchronises for the sizes and for the flags."""
+    _require_device()
+    ws = Workspace(batch.nblk)
+    probe = DecodedBlocks(batch.nblk, 0, 0, 0)
+    count_blocks(batch, probe, ws, stream)
+    torch.cuda.synchronize()
+    nr, kb, _, _ = probe.totals_host()
+    out = DecodedBlocks(batch.nblk, nr, kb, 0, device=batch.data.device, values=False)
+    val_pos = torch.zeros(max(nr, 1), dtype=torch.int32, device=batch.data.device)
+    decode_positions_into(batch, out, val_pos, ws, stream)
+    torch.cuda.synchronize()
+    flags = out.totals_host()[3]   # raises LaunchTimeout on bit 1
+    if flags & FLAG_OVERFLOW:
+        raise RuntimeError("mtblx_decode_blocks_valpos: outputs sized by the count pass overflowed")
+    return out, val_pos[:nr]
 
 
 VERIFY_FUSED = 2

@@ -42,8 +42,14 @@ class PinnedArray:
 class HostOutputs:
     """mtblx_decoded in (pinned) host memory: the caller's byte slices."""
 
-    def __init__(self, nblk: int, rec_cap: int, keys_cap: int, vals_cap: int, pinned: bool = True):
+    def __init__(self, nblk: int, rec_cap: int, keys_cap: int, vals_cap: int, pinned: bool = True,
+                 positions: bool = False):
+        """positions=True: outputs of HostPipe.decode_positions -- a val_pos array (u32 per
+        record) and no value buffer (vals_cap is ignored; `vals` is NULL in the C struct)."""
         mk = (lambda n, dt: PinnedArray(n, dt)) if pinned else (lambda n, dt: _Plain(n, dt))
+        self.positions = bool(positions)
+        if self.positions:
+            vals_cap = 0
         self._bufs = [mk(nblk, np.uint32), mk(nblk, np.uint64), mk(nblk, np.uint64), mk(nblk, np.uint64),
                       mk(nblk, np.int32), mk(rec_cap, np.uint32), mk(rec_cap, np.uint32), mk(keys_cap, np.uint8),
                       mk(vals_cap, np.uint8), mk(4, np.uint64)]
@@ -52,8 +58,25 @@ class HostOutputs:
         self.nblk = nblk
         self.rec_cap, self.keys_cap, self.vals_cap = int(rec_cap), int(keys_cap), int(vals_cap)
         p = [b.a.ctypes.data for b in self._bufs]
-        self.c = Decoded(p[0], p[1], p[2], p[3], p[4], p[5], p[6], self.rec_cap, p[7], self.keys_cap, p[8],
-                         self.vals_cap, p[9])
+        self.c = Decoded(p[0], p[1], p[2], p[3], p[4], p[5], p[6], self.rec_cap, p[7], self.keys_cap,
+                         0 if self.positions else p[8], self.vals_cap, p[9])
+        self._vp = mk(rec_cap, np.uint32) if self.positions else None
+        self.val_pos = self._vp.a if self.positions else None
+        if self.positions:   # no value buffer in this mode
+            self._bufs[8] = self.vals = None
+
+    def records_from(self, b: int, file: np.ndarray, blk_off: np.ndarray):
+        """records(b) of a positions decode: each value is read from `file` (the bytes the pipe
+        decoded) through val_pos -- file[blk_off[b] + val_pos[r] : ... + len]."""
+        out = []
+        r0, kb, base = int(self.rec_base[b]), int(self.key_base[b]), int(blk_off[b])
+        pk = pv = 0
+        for i in range(int(self.nrec[b])):
+            ke, ve = int(self.key_end[r0 + i]), int(self.val_end[r0 + i])
+            at = base + int(self.val_pos[r0 + i])
+            out.append((bytes(self.keys[kb + pk: kb + ke]), bytes(file[at: at + ve - pv])))
+            pk, pv = ke, ve
+        return out
 
     def records(self, b: int):
         out = []
@@ -98,6 +121,25 @@ class HostPipe:
             raise codec.LaunchTimeout("mtblx_pipe_decode: a chunk's decode timed out twice (look-back)")
         if rc != 0:
             raise RuntimeError(f"mtblx_pipe_decode failed: {rc}")
+        return self.stats
+
+    def decode_positions(self, file: np.ndarray, blk_off: np.ndarray, blk_len: np.ndarray,
+                         out: HostOutputs) -> PipeStats:
+        """decode() of an uncompressed file with the values left in `file`
+        (mtblx_pipe_decode_valpos): out = HostOutputs(..., positions=True); out.val_pos[r] is the
+        offset of record r's value in its block, out.records_from reads through it."""
+        if not out.positions:
+            raise ValueError("decode_positions needs HostOutputs(..., positions=True)")
+        f = np.ascontiguousarray(file, np.uint8)
+        off = np.ascontiguousarray(blk_off, np.uint64)
+        ln = np.ascontiguousarray(blk_len, np.uint32)
+        rc = _lib.lib().mtblx_pipe_decode_valpos(self._p, f.ctypes.data, f.size, off.ctypes.data, ln.ctypes.data,
+                                                 off.size, C.byref(out.c), out.val_pos.ctypes.data,
+                                                 C.byref(self.stats))
+        if rc == _lib.MTBLX_E_TIMEOUT:
+            raise codec.LaunchTimeout("mtblx_pipe_decode_valpos: a chunk's decode timed out twice (look-back)")
+        if rc != 0:
+            raise RuntimeError(f"mtblx_pipe_decode_valpos failed: {rc}")
         return self.stats
 
     def __del__(self):
