@@ -13,6 +13,8 @@
 //   Reader::into_iter / iter_prefix / iter_range / iter_from             blocks the iteration reaches,
 //                                                                        records served on the host)
 //   Metadata                    src/metadata.rs:11-24
+//   MergerBuilder / Merger      src/merger.rs:66-260                    (mtblx_merge_plan / _emit: the k-way
+//                                                                        merge and the grouping on the device)
 //   MtblError                   src/error.rs:44-52
 //
 // Errors: where the crate returns Err(Error::Mtbl(e)) this throws mtbl::Error(e); where it
@@ -26,6 +28,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -1144,5 +1147,198 @@ inline std::optional<Bytes> Reader::get(const uint8_t* key, size_t klen) const {
   if (st == MTBLX_GET_ERR) throw Error(MtblError::InvalidBlock);
   throw Panic(st == MTBLX_GET_LOOP ? "Reader::get never returns" : "Reader::get panics");
 }
+
+// ------------------------------------------------------------------ Merger (src/merger.rs)
+// MergerBuilder / Merger (src/merger.rs:66-157) over the device merge (mtblx_merge_plan /
+// mtblx_merge_emit, csrc/merge.hip).  The sources' records are read through Reader::into_iter
+// (an Err or a panic of a source's scan throws here, where the reference returns Err from
+// into_merge_iter / fill), uploaded, merged and grouped on the device, and the items served on
+// the host.  Promised on top of the reference (mtblx.h): the values of a key are in the order the
+// sources were added; the empty-key quirk of :182-186 is kept; an out-of-order source throws
+// UnsortedSource (the reference does not check).  More than MTBLX_MERGE_MAX_SOURCES sources are
+// merged in rounds with the same mode; a merge function is called once, at the end, and never
+// for a group of one (:200-207).
+struct MergeConcat {};   // the group's values joined in source order (the reference's test merge function)
+struct MergeFirst {};    // the first-added source's value
+struct MergeLast {};     // the last-added source's value
+using MergeFn = std::function<Bytes(const Bytes& key, const std::vector<Bytes>& values)>;
+struct UnsortedSource : std::runtime_error {
+  UnsortedSource() : std::runtime_error("merge source out of order") {}
+};
+
+namespace detail {
+struct HostGroups {   // mtblx_merged on the host; ge is empty in the single-value modes
+  Bytes keys, vals;
+  std::vector<uint64_t> ke, ve, ge;
+};
+// one plan + emit over sources [i0, i1) (at most MTBLX_MERGE_MAX_SOURCES)
+inline HostGroups merge_once(const std::vector<HostGroups>& src, size_t i0, size_t i1, int mode) {
+  const uint32_t ns = static_cast<uint32_t>(i1 - i0);
+  std::vector<DevBuf> bufs;
+  std::vector<mtblx_records> recs(ns ? ns : 1);
+  uint64_t n = 0;
+  for (uint32_t i = 0; i < ns; ++i) {
+    const HostGroups& s = src[i0 + i];
+    bufs.push_back(upload(s.keys.data(), s.keys.size()));
+    bufs.push_back(upload(s.ke.data(), s.ke.size()));
+    bufs.push_back(upload(s.vals.data(), s.vals.size()));
+    bufs.push_back(upload(s.ve.data(), s.ve.size()));
+    const size_t b = bufs.size() - 4;
+    recs[i] = mtblx_records{bufs[b].as<uint8_t>(), bufs[b + 1].as<uint64_t>(), bufs[b + 2].as<uint8_t>(),
+                            bufs[b + 3].as<uint64_t>(), s.ke.size()};
+    n += s.ke.size();
+  }
+  const size_t wsb = mtblx_merge_workspace_bytes(n, ns);
+  if (!wsb) throw std::length_error("merge: 2^32 - 16 records or more");
+  DevBuf ws(wsb);
+  uint64_t tot[6] = {};
+  const int rc = mtblx_merge_plan(recs.data(), ns, tot, ws.p, wsb, nullptr);
+  if (rc == MTBLX_E_FORMAT) throw UnsortedSource();
+  abi_check(rc, "mtblx_merge_plan");
+  const bool grouped = mode == MTBLX_MERGE_GROUPS;
+  const uint64_t nve = grouped ? tot[2] : tot[0], nge = grouped ? tot[0] : 0;
+  DevBuf k(tot[1]), ke(8 * tot[0]), v(tot[3]), ve(8 * nve), ge(8 * nge), fl(4);
+  const mtblx_merged out{k.as<uint8_t>(),  tot[1],  ke.as<uint64_t>(), 8 * tot[0], v.as<uint8_t>(), tot[3],
+                         ve.as<uint64_t>(), 8 * nve, ge.as<uint64_t>(), 8 * nge,    fl.as<uint32_t>()};
+  abi_check(mtblx_merge_emit(recs.data(), ns, mode, &out, ws.p, wsb, nullptr), "mtblx_merge_emit");
+  hip_check(hipDeviceSynchronize(), "sync");
+  if (download<uint32_t>(fl.p, 1)[0]) throw std::runtime_error("mtblx_merge_emit: flags set");
+  HostGroups r;
+  r.ke = download<uint64_t>(ke.p, tot[0]);
+  r.ve = download<uint64_t>(ve.p, nve);
+  r.ge = download<uint64_t>(ge.p, nge);
+  r.keys = download<uint8_t>(k.p, tot[1]);
+  r.vals = download<uint8_t>(v.p, r.ve.empty() ? 0 : r.ve.back());
+  return r;
+}
+// grouped results of consecutive source chunks -> the grouped result of all their sources: the
+// groups' value bytes joined per key (CONCAT), and the groups' value lengths joined the same way
+inline HostGroups regroup(const std::vector<HostGroups>& parts, size_t i0, size_t i1) {
+  std::vector<HostGroups> a(i1 - i0), b(i1 - i0);
+  for (size_t i = i0; i < i1; ++i) {
+    const HostGroups& p = parts[i];
+    HostGroups &x = a[i - i0], &y = b[i - i0];
+    x.keys = y.keys = p.keys;
+    x.ke = y.ke = p.ke;
+    x.vals = p.vals;
+    for (uint64_t g : p.ge) {
+      x.ve.push_back(p.ve[g - 1]);
+      y.ve.push_back(8 * g);
+    }
+    y.vals.resize(8 * p.ve.size());
+    for (size_t j = 0; j < p.ve.size(); ++j) {
+      const uint64_t len = p.ve[j] - (j ? p.ve[j - 1] : 0);
+      std::memcpy(y.vals.data() + 8 * j, &len, 8);
+    }
+  }
+  HostGroups va = merge_once(a, 0, a.size(), MTBLX_MERGE_CONCAT);
+  const HostGroups vb = merge_once(b, 0, b.size(), MTBLX_MERGE_CONCAT);
+  HostGroups r;
+  r.keys = std::move(va.keys);
+  r.ke = std::move(va.ke);
+  r.vals = std::move(va.vals);
+  uint64_t end = 0;
+  for (size_t j = 0; j < vb.vals.size() / 8; ++j) {
+    uint64_t len;
+    std::memcpy(&len, vb.vals.data() + 8 * j, 8);
+    r.ve.push_back(end += len);
+  }
+  for (uint64_t e : vb.ve) r.ge.push_back(e / 8);
+  return r;
+}
+inline HostGroups merge_all(std::vector<HostGroups> src, int mode) {
+  bool first = true;
+  while (first || src.size() > 1) {
+    std::vector<HostGroups> next;
+    for (size_t i = 0; i < src.size() || (first && src.empty() && next.empty()); i += MTBLX_MERGE_MAX_SOURCES) {
+      const size_t e = std::min(src.size(), i + MTBLX_MERGE_MAX_SOURCES);
+      next.push_back(mode == MTBLX_MERGE_GROUPS && !first ? regroup(src, i, e) : merge_once(src, i, e, mode));
+    }
+    src = std::move(next);
+    first = false;
+  }
+  return std::move(src[0]);
+}
+inline Bytes slice(const Bytes& b, const std::vector<uint64_t>& end, size_t i) {
+  return Bytes(b.begin() + (i ? end[i - 1] : 0), b.begin() + end[i]);
+}
+}  // namespace detail
+
+class Merger;
+class MergerBuilder {   // src/merger.rs:66-94
+ public:
+  explicit MergerBuilder(MergeFn f) : mode_(MTBLX_MERGE_GROUPS), fn_(std::move(f)) {}
+  explicit MergerBuilder(MergeConcat) : mode_(MTBLX_MERGE_CONCAT) {}
+  explicit MergerBuilder(MergeFirst) : mode_(MTBLX_MERGE_FIRST) {}
+  explicit MergerBuilder(MergeLast) : mode_(MTBLX_MERGE_LAST) {}
+  MergerBuilder& add(Reader source) { push(std::move(source)); return *this; }
+  void push(Reader source) { sources_.push_back(std::move(source)); }
+  MergerBuilder& extend(std::vector<Reader> sources) {
+    for (Reader& r : sources) sources_.push_back(std::move(r));
+    return *this;
+  }
+  Merger build();
+
+ private:
+  int mode_;
+  MergeFn fn_;
+  std::vector<Reader> sources_;
+};
+
+class Merger {
+ public:
+  template <class F>
+  static MergerBuilder builder(F merge) { return MergerBuilder(std::move(merge)); }
+  // MultiIter (:216-260) drained: (key, values) per distinct key, the values in source order
+  std::vector<std::pair<Bytes, std::vector<Bytes>>> into_iter() const {
+    const detail::HostGroups g = run(MTBLX_MERGE_GROUPS);
+    std::vector<std::pair<Bytes, std::vector<Bytes>>> out;
+    for (size_t i = 0; i < g.ke.size(); ++i) {
+      std::vector<Bytes> vs;
+      for (uint64_t j = i ? g.ge[i - 1] : 0; j < g.ge[i]; ++j) vs.push_back(detail::slice(g.vals, g.ve, j));
+      out.emplace_back(detail::slice(g.keys, g.ke, i), std::move(vs));
+    }
+    return out;
+  }
+  // MergerIter (:159-214) drained: (key, merged value) per distinct key
+  std::vector<std::pair<Bytes, Bytes>> into_merge_iter() const {
+    std::vector<std::pair<Bytes, Bytes>> out;
+    if (mode_ == MTBLX_MERGE_GROUPS) {
+      for (auto& kv : into_iter())
+        out.emplace_back(std::move(kv.first), kv.second.size() == 1 ? std::move(kv.second[0]) : fn_(kv.first, kv.second));
+      return out;
+    }
+    const detail::HostGroups g = run(mode_);
+    for (size_t i = 0; i < g.ke.size(); ++i)
+      out.emplace_back(detail::slice(g.keys, g.ke, i), detail::slice(g.vals, g.ve, i));
+    return out;
+  }
+  // src/merger.rs:149-156
+  void write_into(Writer& w) const {
+    for (const auto& kv : into_merge_iter()) w.insert(kv.first, kv.second);
+  }
+
+ private:
+  friend class MergerBuilder;
+  Merger(int mode, MergeFn fn, std::vector<Reader> s) : mode_(mode), fn_(std::move(fn)), sources_(std::move(s)) {}
+  detail::HostGroups run(int mode) const {
+    std::vector<detail::HostGroups> src(sources_.size());
+    for (size_t i = 0; i < sources_.size(); ++i) {
+      ReaderIntoIter it = sources_[i].into_iter();
+      detail::HostGroups& s = src[i];
+      while (auto r = it.next()) {
+        s.keys.insert(s.keys.end(), r->key, r->key + r->key_len);
+        s.vals.insert(s.vals.end(), r->val, r->val + r->val_len);
+        s.ke.push_back(s.keys.size());
+        s.ve.push_back(s.vals.size());
+      }
+    }
+    return detail::merge_all(std::move(src), mode);
+  }
+  int mode_;
+  MergeFn fn_;
+  std::vector<Reader> sources_;
+};
+inline Merger MergerBuilder::build() { return Merger(mode_, std::move(fn_), std::move(sources_)); }
 
 }  // namespace mtbl

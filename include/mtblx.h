@@ -37,8 +37,8 @@ extern "C" {
 #endif
 
 #define MTBLX_ABI_VERSION 3   /* 3: the block cut takes a caller-owned workspace (round 6).  Still 3 with
-                                 mtblx_decode_blocks_valpos / mtblx_pipe_decode_valpos: two added
-                                 symbols, no existing one changed */
+                                 mtblx_decode_blocks_valpos / mtblx_pipe_decode_valpos and with the
+                                 mtblx_merge_* calls: added symbols, no existing one changed */
 
 /* ---- API return codes ---- */
 #define MTBLX_OK 0
@@ -451,6 +451,79 @@ int mtblx_encode_index(const mtblx_records* rec, const uint64_t* blk_rec, uint32
                        uint32_t restart_interval, const uint8_t* data, uint64_t region_off, uint64_t data_bytes,
                        const uint64_t* blk_off, const uint32_t* blk_len, uint8_t* file, uint64_t file_cap,
                        uint64_t* file_len, void* stream);
+
+/* ---- Merger on the device: k-way merge of sorted sources, duplicate keys grouped (src/merger.rs) ----
+ * nsrc sources (host array of mtblx_records with device pointers, keys strictly increasing within a
+ * source; keys / vals may be NULL where every key / value of the source is empty) are merged into
+ * what MergerIter / MultiIter yield (src/merger.rs:172-260): one item per distinct key, in key
+ * order (unsigned bytes, then length: Vec<u8>::cmp), carrying every source's value for that key.
+ *  - Order inside a group.  The reference drains a BinaryHeap whose Ord looks at the key only
+ *    (:45-49), so its order of equal keys is unspecified; what is taken from it is the order of
+ *    keys and the multiset of values per key.  This library promises more: the values of a group
+ *    are in source order (the order of `src`).
+ *  - The empty-key quirk (:182-186, :236-240: cur_key.is_empty() doubles as "no current key").  The
+ *    records with the empty key (at most one per source, its first) vanish -- key and values --
+ *    when any other record exists; when none does, one item ("", [v]) comes out, v being the value
+ *    taken last and the merge function not called.  Where the reference's v depends on heap order
+ *    (two or more sources, each holding only the empty key), v here is the highest-numbered
+ *    source's.  totals[4] counts the records dropped this way.
+ *  - An out-of-order source (a key <= its predecessor) is refused: mtblx_merge_plan returns
+ *    MTBLX_E_FORMAT with MTBLX_MERGE_UNSORTED in totals[5] (other totals 0).  The reference does
+ *    not check; its output for such input is an accident of the heap and is not reproduced.
+ *  - Limits: at most MTBLX_MERGE_MAX_SOURCES sources per call (more: MTBLX_E_INVAL; merge in rounds
+ *    with the same mode, exact because source order is kept -- mtblx/merger.py and mtbl.hpp do),
+ *    fewer than MTBLX_MERGE_MAX_RECORDS records in all sources together (u32 handles).
+ * Two calls: mtblx_merge_plan (synchronous) builds one 16-byte handle per record, merges the handles
+ * in ceil(log2 nsrc) passes, finds the groups and returns the output sizes in totals (host, 6 words):
+ *   [0] groups  [1] key bytes of the groups  [2] values in all groups  [3] value bytes in all groups
+ *   [4] records dropped by the empty-key quirk  [5] flags (MTBLX_MERGE_UNSORTED / _INTERNAL)
+ * which size every mode's output exactly: keys [1] bytes, key_end [0] entries; GROUPS: vals [3]
+ * bytes, val_end [2] entries, grp_end [0] entries; CONCAT: vals [3] bytes, val_end [0] entries;
+ * FIRST / LAST: val_end [0] entries and vals at most [3] bytes (an upper bound: the bytes written
+ * are val_end[groups - 1]).  mtblx_merge_emit (asynchronous) then reads the planned workspace with
+ * the same sources and writes the outputs.  The workspace (device, 256-byte aligned,
+ * mtblx_merge_workspace_bytes; no fill needed; one call at a time) holds the two handle arrays and
+ * the grouping arrays, ~90 B per record.  nsrc == 0 and sources with n == 0 are legal. */
+#define MTBLX_MERGE_MAX_SOURCES 64
+#define MTBLX_MERGE_MAX_RECORDS 0xFFFFFFF0ull   /* 2^32 - 16 */
+#define MTBLX_MERGE_GROUPS 0   /* MultiIter: key g has values grp_end[g-1] .. grp_end[g], one val_end per value */
+#define MTBLX_MERGE_CONCAT 1   /* one value per key: the group's values joined in source order (the merge
+                                  function of the reference's own tests, src/merger.rs:269-275)            */
+#define MTBLX_MERGE_FIRST 2    /* the lowest-numbered source's value (oldest wins)                        */
+#define MTBLX_MERGE_LAST 3     /* the highest-numbered source's value (newest wins)                       */
+#define MTBLX_MERGE_UNSORTED 1u     /* totals[5]: a source's key <= its predecessor                      */
+#define MTBLX_MERGE_INTERNAL 2u     /* totals[5]: a merge pass met a split it could not use (a bug)      */
+#define MTBLX_MERGE_OVERFLOW 1u     /* *flags of mtblx_merge_emit: a capacity was too small              */
+#define MTBLX_MERGE_NOT_PLANNED 2u  /* *flags: the workspace is not that of a successful mtblx_merge_plan
+                                       over sources of these record counts; nothing was written          */
+/* Output of mtblx_merge_emit.  Every capacity is in BYTES; an entry or a key / value that does not
+ * fit entirely is not written at all (MTBLX_MERGE_OVERFLOW in *flags), nothing past a capacity is.
+ * In the three single-value modes keys / key_end / vals / val_end are exactly an mtblx_records of
+ * totals[0] records: they feed mtblx_encode_plan / mtblx_encode_blocks with no reshaping. */
+typedef struct mtblx_merged {
+  uint8_t* keys;       /* device: key of group g = keys[key_end[g-1] .. key_end[g])                       */
+  uint64_t keys_cap;
+  uint64_t* key_end;   /* device [groups], u64 END offsets                                               */
+  uint64_t key_end_cap;
+  uint8_t* vals;
+  uint64_t vals_cap;
+  uint64_t* val_end;   /* device, u64 END offsets: [values] in MTBLX_MERGE_GROUPS, else [groups]         */
+  uint64_t val_end_cap;
+  uint64_t* grp_end;   /* device [groups], u64 END index into the value list; MTBLX_MERGE_GROUPS only
+                          (else never written, may be NULL)                                            */
+  uint64_t grp_end_cap;
+  uint32_t* flags;     /* device word, cleared by the call: MTBLX_MERGE_OVERFLOW / _NOT_PLANNED           */
+} mtblx_merged;
+size_t mtblx_merge_workspace_bytes(uint64_t nrec, uint32_t nsrc);
+int mtblx_merge_plan(const mtblx_records* src, uint32_t nsrc, uint64_t* totals, void* workspace, size_t ws_bytes,
+                     void* stream);
+int mtblx_merge_emit(const mtblx_records* src, uint32_t nsrc, int mode, const mtblx_merged* out,
+                     const void* workspace, size_t ws_bytes, void* stream);
+/* diagnostic (scripts/merge_bench.py): mtblx_merge_plan, plus the HIP-event time in ms of each of
+ * its phases: phase_ms[0] the handle build (shared prefix, handles, order check), [1 .. passes] the
+ * merge passes (passes = ceil(log2 nsrc)), [passes + 1] the grouping.  phase_cap >= passes + 2. */
+int mtblx_merge_plan_timed(const mtblx_records* src, uint32_t nsrc, uint64_t* totals, void* workspace,
+                           size_t ws_bytes, void* stream, float* phase_ms, uint32_t phase_cap);
 
 /* ---- snappy raw decompression on the device (f4) ----
  * Reader::block's decompression step for CompressionType::Snappy (src/reader.rs:166-170 ->

@@ -101,6 +101,58 @@ extern "C" int mtblx_decode_blocks_verify(const mtblx_block_batch* in, const mtb
   return mtblx_crc32c_blocks(in, crc, crc_bad, framed & 1, stream);
 }
 
+// ---- Merger (csrc/merge.hip): the argument checks need no device ----
+extern "C" size_t mtblx_merge_impl_ws_bytes(uint64_t nrec);
+extern "C" int mtblx_merge_impl_plan(const mtblx_records* src, uint32_t nsrc, uint64_t* totals, void* ws,
+                                     hipStream_t s, float* phase_ms, uint32_t phase_cap);
+extern "C" int mtblx_merge_impl_emit(const mtblx_records* src, uint32_t nsrc, int mode, const mtblx_merged* out,
+                                     const void* ws, hipStream_t s);
+
+extern "C" size_t mtblx_merge_workspace_bytes(uint64_t nrec, uint32_t nsrc) {
+  (void)nsrc;   // the source table travels in the kernel arguments
+  if (nrec >= MTBLX_MERGE_MAX_RECORDS) return 0;
+  return mtblx_merge_impl_ws_bytes(nrec);
+}
+
+static int merge_check(const mtblx_records* src, uint32_t nsrc, const void* ws, size_t wsb) {
+  if (nsrc > MTBLX_MERGE_MAX_SOURCES || (nsrc && !src)) return MTBLX_E_INVAL;
+  if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0) return MTBLX_E_INVAL;
+  uint64_t n = 0;
+  for (uint32_t i = 0; i < nsrc; ++i) {
+    if (src[i].n >= MTBLX_MERGE_MAX_RECORDS) return MTBLX_E_INVAL;
+    n += src[i].n;
+  }
+  if (n >= MTBLX_MERGE_MAX_RECORDS || wsb < mtblx_merge_impl_ws_bytes(n)) return MTBLX_E_INVAL;
+  return MTBLX_OK;
+}
+
+extern "C" int mtblx_merge_plan(const mtblx_records* src, uint32_t nsrc, uint64_t* totals, void* ws, size_t wsb,
+                                void* stream) {
+  if (!totals) return MTBLX_E_INVAL;
+  const int c = merge_check(src, nsrc, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_merge_impl_plan(src, nsrc, totals, ws, reinterpret_cast<hipStream_t>(stream), nullptr, 0);
+}
+
+extern "C" int mtblx_merge_plan_timed(const mtblx_records* src, uint32_t nsrc, uint64_t* totals, void* ws, size_t wsb,
+                                      void* stream, float* phase_ms, uint32_t phase_cap) {
+  if (!totals || !phase_ms) return MTBLX_E_INVAL;
+  const int c = merge_check(src, nsrc, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_merge_impl_plan(src, nsrc, totals, ws, reinterpret_cast<hipStream_t>(stream), phase_ms, phase_cap);
+}
+
+extern "C" int mtblx_merge_emit(const mtblx_records* src, uint32_t nsrc, int mode, const mtblx_merged* out,
+                                const void* ws, size_t wsb, void* stream) {
+  if (!out || !out->flags || mode < MTBLX_MERGE_GROUPS || mode > MTBLX_MERGE_LAST) return MTBLX_E_INVAL;
+  if ((!out->keys && out->keys_cap) || (!out->key_end && out->key_end_cap) || (!out->vals && out->vals_cap) ||
+      (!out->val_end && out->val_end_cap) || (!out->grp_end && out->grp_end_cap))
+    return MTBLX_E_INVAL;
+  const int c = merge_check(src, nsrc, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_merge_impl_emit(src, nsrc, mode, out, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
 // ---- bounds-checked diagnostic build only (csrc/bounds.h, Makefile target `bounds`) ----
 #ifdef MTBLX_BOUNDS
 #include <stdio.h>

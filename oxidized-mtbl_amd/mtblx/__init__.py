@@ -5,8 +5,18 @@ Package layout
   codec.py    device batch decode (HIP kernels in csrc/decode.hip)
   writer.py   Writer / WriterBuilder mirror of src/writer.rs
   synth.py    deterministic synthetic workloads of BASELINE.json's configs
+  merger.py   Merger / MergerBuilder mirror of src/merger.rs over the device merge (csrc/merge.hip)
 """
 from ._lib import EXPORTS, LIB_PATH, lib  # noqa: F401
 from .writer import CompressionType, OutOfOrderKey, Writer, WriterBuilder  # noqa: F401
 
-__all__ = ["Writer", "WriterBuilder", "CompressionType", "OutOfOrderKey", "lib", "LIB_PATH", "EXPORTS"]
+
+def __getattr__(name):   # Merger / MergerBuilder need torch: imported on first use
+    if name in ("Merger", "MergerBuilder"):
+        from . import merger
+        return getattr(merger, name)
+    raise AttributeError(name)
+
+
+__all__ = ["Writer", "WriterBuilder", "CompressionType", "OutOfOrderKey", "Merger", "MergerBuilder", "lib", "LIB_PATH",
+           "EXPORTS"]

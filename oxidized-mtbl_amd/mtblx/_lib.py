@@ -42,7 +42,12 @@ EXPORTS = [
     "mtblx_codec_available", "mtblx_decompress", "mtblx_compress", "mtblx_decompress_blocks", "mtblx_writer_set_level",
     "mtblx_index_seek_batch", "mtblx_block_seek_batch", "mtblx_block_seek_batch_kbuf", "mtblx_block_seek_batch_ex", "mtblx_copy_ranges", "mtblx_entry_offsets",
     "mtblx_key_filter",
+    "mtblx_merge_workspace_bytes", "mtblx_merge_plan", "mtblx_merge_emit", "mtblx_merge_plan_timed",
 ]
+MERGE_MAX_SOURCES, MERGE_MAX_RECORDS = 64, (1 << 32) - 16
+MERGE_GROUPS, MERGE_CONCAT, MERGE_FIRST, MERGE_LAST = range(4)
+MERGE_UNSORTED, MERGE_INTERNAL = 1, 2          # totals[5] of mtblx_merge_plan
+MERGE_OVERFLOW, MERGE_NOT_PLANNED = 1, 2       # *flags of mtblx_merge_emit
 PLAN_OUT_OF_ORDER, PLAN_PANIC, PLAN_TOO_LONG = 1, 2, 4
 
 
@@ -61,6 +66,12 @@ class Decoded(C.Structure):
 class Records(C.Structure):
     _fields_ = [("keys", C.c_void_p), ("key_end", C.c_void_p), ("vals", C.c_void_p), ("val_end", C.c_void_p),
                 ("n", C.c_uint64)]
+
+
+class Merged(C.Structure):   # mtblx_merged (capacities in bytes)
+    _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("key_end", C.c_void_p), ("key_end_cap", C.c_uint64),
+                ("vals", C.c_void_p), ("vals_cap", C.c_uint64), ("val_end", C.c_void_p), ("val_end_cap", C.c_uint64),
+                ("grp_end", C.c_void_p), ("grp_end_cap", C.c_uint64), ("flags", C.c_void_p)]
 
 
 class PipeStats(C.Structure):
@@ -241,6 +252,15 @@ def lib() -> C.CDLL:
         L.mtblx_key_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_uint64,
                                        C.c_void_p, C.c_void_p]
         L.mtblx_key_filter.restype = C.c_int
+        L.mtblx_merge_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        L.mtblx_merge_workspace_bytes.restype = C.c_size_t
+        L.mtblx_merge_plan.argtypes = [C.POINTER(Records), C.c_uint32, u64p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_merge_plan.restype = C.c_int
+        L.mtblx_merge_plan_timed.argtypes = L.mtblx_merge_plan.argtypes + [C.POINTER(C.c_float), C.c_uint32]
+        L.mtblx_merge_plan_timed.restype = C.c_int
+        L.mtblx_merge_emit.argtypes = [C.POINTER(Records), C.c_uint32, C.c_int, C.POINTER(Merged), C.c_void_p,
+                                       C.c_size_t, C.c_void_p]
+        L.mtblx_merge_emit.restype = C.c_int
         L.mtblx_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_uint64]
         L.mtblx_host_alloc.restype = C.c_int
         L.mtblx_host_free.argtypes = [C.c_void_p]
