@@ -15,7 +15,10 @@
 //   Metadata                    src/metadata.rs:11-24
 //   MergerBuilder / Merger      src/merger.rs:66-260                    (mtblx_merge_plan / _emit: the k-way
 //                                                                        merge and the grouping on the device)
-//   MtblError                   src/error.rs:44-52
+//   SorterBuilder / Sorter      src/sorter.rs:17-258                    (mtblx_sort_plan / _emit: the sort of
+//                                                                        a chunk on the device; the chunks
+//                                                                        merged by the device Merger)
+//   MtblError                  src/error.rs:44-52
 //
 // Errors: where the crate returns Err(Error::Mtbl(e)) this throws mtbl::Error(e); where it
 // returns Err(Error::Io) (a snappy stream snap rejects) it throws mtbl::Error(kIo); where it
@@ -1340,5 +1343,161 @@ class Merger {
   std::vector<Reader> sources_;
 };
 inline Merger MergerBuilder::build() { return Merger(mode_, std::move(fn_), std::move(sources_)); }
+
+// ------------------------------------------------------------------ Sorter (src/sorter.rs)
+// SorterBuilder / Sorter (src/sorter.rs:25-258) over the device sort (mtblx_sort_plan /
+// mtblx_sort_emit, csrc/sort.hip) and detail::merge_all.  insert keeps the reference's memory rule
+// (:128-137); write_chunk (:142-197) is one device sort of the pending records; merge_chunks
+// (:199-233) and the final merge of into_iter (:244-257) are the device Merger over the chunks,
+// oldest first, with its empty-key quirk -- exactly where the reference has it.  Chunks are kept in
+// host memory between the device calls, not in compressed temp files: chunk_compression_type /
+// _level are accepted and stored and have no effect.  Promised on top of the reference (mtblx.h):
+// the values of a key are in insertion order (the reference sorts with sort_unstable_by).  A merge
+// function is never called for a group of one (:166-170).
+constexpr size_t DEFAULT_NB_CHUNKS = 25, MIN_NB_CHUNKS = 1;                              // src/lib.rs:11-12
+constexpr size_t DEFAULT_SORTER_MEMORY = 1073741824, MIN_SORTER_MEMORY = 10485760;       // :13-14
+constexpr size_t INITIAL_SORTER_VEC_SIZE = 131072;                                       // :15
+
+namespace detail {
+// one mtblx_sort_plan + mtblx_sort_emit over one batch of records in any order
+inline HostGroups sort_once(const HostGroups& s, int mode) {
+  const DevBuf dk = upload(s.keys.data(), s.keys.size()), dke = upload(s.ke.data(), s.ke.size()),
+               dv = upload(s.vals.data(), s.vals.size()), dve = upload(s.ve.data(), s.ve.size());
+  const mtblx_records rec{dk.as<uint8_t>(), dke.as<uint64_t>(), dv.as<uint8_t>(), dve.as<uint64_t>(), s.ke.size()};
+  const size_t wsb = mtblx_sort_workspace_bytes(rec.n);
+  if (!wsb) throw std::length_error("sort: 2^32 - 16 records or more");
+  DevBuf ws(wsb);
+  uint64_t tot[6] = {};
+  abi_check(mtblx_sort_plan(&rec, tot, ws.p, wsb, nullptr), "mtblx_sort_plan");
+  const bool grouped = mode == MTBLX_MERGE_GROUPS;
+  const uint64_t nve = grouped ? tot[2] : tot[0], nge = grouped ? tot[0] : 0;
+  DevBuf k(tot[1]), ke(8 * tot[0]), v(tot[3]), ve(8 * nve), ge(8 * nge), fl(4);
+  const mtblx_merged out{k.as<uint8_t>(),  tot[1],  ke.as<uint64_t>(), 8 * tot[0], v.as<uint8_t>(), tot[3],
+                         ve.as<uint64_t>(), 8 * nve, ge.as<uint64_t>(), 8 * nge,    fl.as<uint32_t>()};
+  abi_check(mtblx_sort_emit(&rec, mode, &out, ws.p, wsb, nullptr), "mtblx_sort_emit");
+  hip_check(hipDeviceSynchronize(), "sync");
+  if (download<uint32_t>(fl.p, 1)[0]) throw std::runtime_error("mtblx_sort_emit: flags set");
+  HostGroups r;
+  r.ke = download<uint64_t>(ke.p, tot[0]);
+  r.ve = download<uint64_t>(ve.p, nve);
+  r.ge = download<uint64_t>(ge.p, nge);
+  r.keys = download<uint8_t>(k.p, tot[1]);
+  r.vals = download<uint8_t>(v.p, r.ve.empty() ? 0 : r.ve.back());
+  return r;
+}
+// grouped items -> one record per key: a group of one passes through, fn merges the others
+inline HostGroups apply_fn(const HostGroups& g, const MergeFn& fn) {
+  HostGroups r;
+  for (size_t i = 0; i < g.ke.size(); ++i) {
+    const Bytes key = slice(g.keys, g.ke, i);
+    std::vector<Bytes> vs;
+    for (uint64_t j = i ? g.ge[i - 1] : 0; j < g.ge[i]; ++j) vs.push_back(slice(g.vals, g.ve, j));
+    const Bytes v = vs.size() == 1 ? std::move(vs[0]) : fn(key, vs);
+    r.keys.insert(r.keys.end(), key.begin(), key.end());
+    r.vals.insert(r.vals.end(), v.begin(), v.end());
+    r.ke.push_back(r.keys.size());
+    r.ve.push_back(r.vals.size());
+  }
+  return r;
+}
+}  // namespace detail
+
+class Sorter;
+class SorterBuilder {   // src/sorter.rs:17-70
+ public:
+  explicit SorterBuilder(MergeFn f) : mode_(MTBLX_MERGE_GROUPS), fn_(std::move(f)) {}
+  explicit SorterBuilder(MergeConcat) : mode_(MTBLX_MERGE_CONCAT) {}
+  explicit SorterBuilder(MergeFirst) : mode_(MTBLX_MERGE_FIRST) {}
+  explicit SorterBuilder(MergeLast) : mode_(MTBLX_MERGE_LAST) {}
+  SorterBuilder& max_memory(size_t memory) { max_memory_ = std::max(memory, MIN_SORTER_MEMORY); return *this; }         // :37
+  SorterBuilder& max_nb_chunks(size_t nb_chunks) { max_nb_chunks_ = std::max(nb_chunks, MIN_NB_CHUNKS); return *this; }  // :44
+  SorterBuilder& chunk_compression_type(CompressionType c) { ctype_ = c; return *this; }   // stored, no effect
+  SorterBuilder& chunk_compression_level(uint32_t l) { clevel_ = l; return *this; }        // stored, no effect
+  Sorter build();
+
+ private:
+  int mode_;
+  MergeFn fn_;
+  size_t max_memory_ = DEFAULT_SORTER_MEMORY, max_nb_chunks_ = DEFAULT_NB_CHUNKS;   // :28-29
+  CompressionType ctype_ = CompressionType::Snappy;                                  // :30
+  uint32_t clevel_ = 0;                                                              // :31
+};
+
+class Sorter {
+ public:
+  template <class F>
+  static SorterBuilder builder(F merge) { return SorterBuilder(std::move(merge)); }   // :108-110
+  template <class F>
+  explicit Sorter(F merge);                                                            // :112-114
+  // :120-140
+  void insert(const uint8_t* key, size_t klen, const uint8_t* val, size_t vlen) {
+    entry_bytes_ += klen + vlen;                                       // :128
+    // entries.push (:129) and entries.capacity() (:131): the Vec starts at INITIAL_SORTER_VEC_SIZE,
+    // doubles when a push finds it full and keeps its capacity through drain(..).  The doubling is
+    // std's current amortised growth, an implementation detail, emulated because the rule reads it
+    if (len_ == capacity_) capacity_ *= 2;
+    ++len_;
+    pending_.keys.insert(pending_.keys.end(), key, key + klen);
+    pending_.vals.insert(pending_.vals.end(), val, val + vlen);
+    pending_.ke.push_back(pending_.keys.size());
+    pending_.ve.push_back(pending_.vals.size());
+    if (entry_bytes_ + capacity_ * 32 >= max_memory_) {                // :131-132, 32 = size_of::<Entry>()
+      write_chunk();
+      if (chunks_.size() > max_nb_chunks_) merge_chunks();             // :134-136
+    }
+  }
+  void insert(const Bytes& k, const Bytes& v) { insert(k.data(), k.size(), v.data(), v.size()); }
+  void insert(const std::string& k, const std::string& v) {
+    insert(reinterpret_cast<const uint8_t*>(k.data()), k.size(), reinterpret_cast<const uint8_t*>(v.data()), v.size());
+  }
+  // :244-257, drained: (key, merged value) per distinct key.  Consumes the pending records.
+  std::vector<std::pair<Bytes, Bytes>> into_iter() {
+    write_chunk();                                                     // :246, also when nothing is pending
+    const detail::HostGroups g = merged();                             // :253-256; no merge_chunks here
+    std::vector<std::pair<Bytes, Bytes>> out;
+    for (size_t i = 0; i < g.ke.size(); ++i)
+      out.emplace_back(detail::slice(g.keys, g.ke, i), detail::slice(g.vals, g.ve, i));
+    return out;
+  }
+  // :235-242
+  void write_into(Writer& w) {
+    for (const auto& kv : into_iter()) w.insert(kv.first, kv.second);
+  }
+  const std::vector<size_t>& chunk_sizes() const { return chunk_sizes_; }   // records per write_chunk, in order
+  size_t merges() const { return merges_; }                                // runs of merge_chunks
+
+ private:
+  friend class SorterBuilder;
+  Sorter(int mode, MergeFn fn, size_t max_memory, size_t max_nb_chunks)
+      : mode_(mode), fn_(std::move(fn)), max_memory_(max_memory), max_nb_chunks_(max_nb_chunks) {}
+  void write_chunk() {                                                 // :142-197
+    chunk_sizes_.push_back(pending_.ke.size());
+    chunks_.push_back(mode_ == MTBLX_MERGE_GROUPS ? detail::apply_fn(detail::sort_once(pending_, mode_), fn_)
+                                                  : detail::sort_once(pending_, mode_));
+    pending_ = detail::HostGroups();
+    entry_bytes_ = 0;                                                  // :192
+    len_ = 0;                                                          // :155 drain(..): the capacity stays
+  }
+  detail::HostGroups merged() const {   // a Merger over the chunks, oldest first
+    return mode_ == MTBLX_MERGE_GROUPS ? detail::apply_fn(detail::merge_all(chunks_, mode_), fn_)
+                                       : detail::merge_all(chunks_, mode_);
+  }
+  void merge_chunks() {                                                // :199-233: the result is the only, hence oldest, chunk
+    detail::HostGroups m = merged();
+    chunks_.clear();
+    chunks_.push_back(std::move(m));
+    ++merges_;
+  }
+  int mode_;
+  MergeFn fn_;
+  size_t max_memory_, max_nb_chunks_;
+  std::vector<detail::HostGroups> chunks_;
+  detail::HostGroups pending_;
+  size_t entry_bytes_ = 0, len_ = 0, capacity_ = INITIAL_SORTER_VEC_SIZE, merges_ = 0;
+  std::vector<size_t> chunk_sizes_;
+};
+inline Sorter SorterBuilder::build() { return Sorter(mode_, std::move(fn_), max_memory_, max_nb_chunks_); }
+template <class F>
+inline Sorter::Sorter(F merge) : Sorter(SorterBuilder(std::move(merge)).build()) {}
 
 }  // namespace mtbl

@@ -38,7 +38,7 @@ extern "C" {
 
 #define MTBLX_ABI_VERSION 3   /* 3: the block cut takes a caller-owned workspace (round 6).  Still 3 with
                                  mtblx_decode_blocks_valpos / mtblx_pipe_decode_valpos and with the
-                                 mtblx_merge_* calls: added symbols, no existing one changed */
+                                 mtblx_merge_* and mtblx_sort_* calls: added symbols, no existing one changed */
 
 /* ---- API return codes ---- */
 #define MTBLX_OK 0
@@ -524,6 +524,41 @@ int mtblx_merge_emit(const mtblx_records* src, uint32_t nsrc, int mode, const mt
  * merge passes (passes = ceil(log2 nsrc)), [passes + 1] the grouping.  phase_cap >= passes + 2. */
 int mtblx_merge_plan_timed(const mtblx_records* src, uint32_t nsrc, uint64_t* totals, void* workspace,
                            size_t ws_bytes, void* stream, float* phase_ms, uint32_t phase_cap);
+
+/* ---- Sorter on the device: one batch of unsorted records, duplicate keys grouped (src/sorter.rs) ----
+ * `in` is ONE mtblx_records batch on the device: keys in any order, duplicate keys and empty keys
+ * allowed, keys / vals NULL where every key / value is empty, n < MTBLX_MERGE_MAX_RECORDS.  The
+ * result is what Sorter::write_chunk (src/sorter.rs:142-197) writes for these records: keys
+ * ascending by Vec<u8>::cmp, one item per distinct key.  totals[0..5], mtblx_merged, the four
+ * MTBLX_MERGE_* modes, MTBLX_MERGE_OVERFLOW / _NOT_PLANNED and the two-call shape (plan synchronous,
+ * emit asynchronous, every capacity in bytes) are those of mtblx_merge_*, with two differences:
+ *  - The values of a key come out in INPUT order (record index), so FIRST / LAST are the first /
+ *    last inserted and CONCAT joins in insertion order.  The reference promises nothing here
+ *    (sort_unstable_by, :152); this library promises stability, as the merge promises source order.
+ *  - No empty-key quirk in this call: write_chunk keeps its current key in an Option (:154-188),
+ *    not behind cur_key.is_empty(), so the empty-key group is kept like any other and totals[4] is
+ *    always 0.  The quirk enters where the reference has it: in the Merger that the Sorter runs
+ *    over its chunks (mtblx/sorter.py, mtbl::Sorter).  There is no order to check either:
+ *    totals[5] can only carry MTBLX_MERGE_INTERNAL.
+ * How: the bytes every key shares are found by one pass over all keys (the minimum common prefix
+ * with record 0's key); workgroups sort tiles of MTBLX_SORT_TILE handles in LDS into sorted runs;
+ * ceil(log2 ceil(n / MTBLX_SORT_TILE)) passes of the Merger's merge pass join the runs; grouping
+ * and gather are the Merger's.  The workspace (device, 256-byte aligned,
+ * mtblx_sort_workspace_bytes; no fill needed; one call at a time) has the Merger's layout, ~90 B
+ * per record; its planned mark differs from the Merger's, so an emit of one kind over a workspace
+ * planned by the other reports MTBLX_MERGE_NOT_PLANNED and writes nothing.  n == 0 is legal.
+ * MTBLX_E_INVAL, before any device work: NULL or misaligned workspace, workspace too small, bad
+ * mode, n >= MTBLX_MERGE_MAX_RECORDS, n != 0 with a NULL END array. */
+#define MTBLX_SORT_TILE 1024   /* handles per tile-sorted run (csrc/merge_dev.h kSortTile) */
+size_t mtblx_sort_workspace_bytes(uint64_t nrec);
+int mtblx_sort_plan(const mtblx_records* in, uint64_t* totals, void* workspace, size_t ws_bytes, void* stream);
+int mtblx_sort_emit(const mtblx_records* in, int mode, const mtblx_merged* out, const void* workspace,
+                    size_t ws_bytes, void* stream);
+/* diagnostic (scripts/sort_bench.py): mtblx_sort_plan, plus the HIP-event time in ms of each of its
+ * phases: phase_ms[0] the shared-prefix scan, [1] the tile sort (handles built and sorted in LDS),
+ * [2 .. passes + 1] the merge passes, [passes + 2] the grouping.  phase_cap >= passes + 3. */
+int mtblx_sort_plan_timed(const mtblx_records* in, uint64_t* totals, void* workspace, size_t ws_bytes, void* stream,
+                          float* phase_ms, uint32_t phase_cap);
 
 /* ---- snappy raw decompression on the device (f4) ----
  * Reader::block's decompression step for CompressionType::Snappy (src/reader.rs:166-170 ->

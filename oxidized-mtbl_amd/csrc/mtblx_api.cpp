@@ -153,6 +153,52 @@ extern "C" int mtblx_merge_emit(const mtblx_records* src, uint32_t nsrc, int mod
   return mtblx_merge_impl_emit(src, nsrc, mode, out, ws, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- Sorter (csrc/sort.hip): one batch of unsorted records; the argument checks need no device ----
+extern "C" size_t mtblx_sort_impl_ws_bytes(uint64_t nrec);
+extern "C" int mtblx_sort_impl_plan(const mtblx_records* in, uint64_t* totals, void* ws, hipStream_t s,
+                                    float* phase_ms, uint32_t phase_cap);
+extern "C" int mtblx_sort_impl_emit(const mtblx_records* in, int mode, const mtblx_merged* out, const void* ws,
+                                    hipStream_t s);
+
+extern "C" size_t mtblx_sort_workspace_bytes(uint64_t nrec) {
+  if (nrec >= MTBLX_MERGE_MAX_RECORDS) return 0;
+  return mtblx_sort_impl_ws_bytes(nrec);
+}
+
+static int sort_check(const mtblx_records* in, const void* ws, size_t wsb) {
+  if (!in || in->n >= MTBLX_MERGE_MAX_RECORDS) return MTBLX_E_INVAL;
+  if (in->n && (!in->key_end || !in->val_end)) return MTBLX_E_INVAL;
+  if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0) return MTBLX_E_INVAL;
+  if (wsb < mtblx_sort_impl_ws_bytes(in->n)) return MTBLX_E_INVAL;
+  return MTBLX_OK;
+}
+
+extern "C" int mtblx_sort_plan(const mtblx_records* in, uint64_t* totals, void* ws, size_t wsb, void* stream) {
+  if (!totals) return MTBLX_E_INVAL;
+  const int c = sort_check(in, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_sort_impl_plan(in, totals, ws, reinterpret_cast<hipStream_t>(stream), nullptr, 0);
+}
+
+extern "C" int mtblx_sort_plan_timed(const mtblx_records* in, uint64_t* totals, void* ws, size_t wsb, void* stream,
+                                     float* phase_ms, uint32_t phase_cap) {
+  if (!totals || !phase_ms) return MTBLX_E_INVAL;
+  const int c = sort_check(in, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_sort_impl_plan(in, totals, ws, reinterpret_cast<hipStream_t>(stream), phase_ms, phase_cap);
+}
+
+extern "C" int mtblx_sort_emit(const mtblx_records* in, int mode, const mtblx_merged* out, const void* ws, size_t wsb,
+                               void* stream) {
+  if (!out || !out->flags || mode < MTBLX_MERGE_GROUPS || mode > MTBLX_MERGE_LAST) return MTBLX_E_INVAL;
+  if ((!out->keys && out->keys_cap) || (!out->key_end && out->key_end_cap) || (!out->vals && out->vals_cap) ||
+      (!out->val_end && out->val_end_cap) || (!out->grp_end && out->grp_end_cap))
+    return MTBLX_E_INVAL;
+  const int c = sort_check(in, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_sort_impl_emit(in, mode, out, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
 // ---- bounds-checked diagnostic build only (csrc/bounds.h, Makefile target `bounds`) ----
 #ifdef MTBLX_BOUNDS
 #include <stdio.h>

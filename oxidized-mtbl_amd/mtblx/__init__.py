@@ -6,17 +6,21 @@ Package layout
   writer.py   Writer / WriterBuilder mirror of src/writer.rs
   synth.py    deterministic synthetic workloads of BASELINE.json's configs
   merger.py   Merger / MergerBuilder mirror of src/merger.rs over the device merge (csrc/merge.hip)
+  sorter.py   Sorter / SorterBuilder mirror of src/sorter.rs over the device sort (csrc/sort.hip)
 """
 from ._lib import EXPORTS, LIB_PATH, lib  # noqa: F401
 from .writer import CompressionType, OutOfOrderKey, Writer, WriterBuilder  # noqa: F401
 
 
-def __getattr__(name):   # Merger / MergerBuilder need torch: imported on first use
+def __getattr__(name):   # Merger / MergerBuilder / Sorter / SorterBuilder need torch: imported on first use
     if name in ("Merger", "MergerBuilder"):
         from . import merger
         return getattr(merger, name)
+    if name in ("Sorter", "SorterBuilder"):
+        from . import sorter
+        return getattr(sorter, name)
     raise AttributeError(name)
 
 
-__all__ = ["Writer", "WriterBuilder", "CompressionType", "OutOfOrderKey", "Merger", "MergerBuilder", "lib", "LIB_PATH",
-           "EXPORTS"]
+__all__ = ["Writer", "WriterBuilder", "CompressionType", "OutOfOrderKey", "Merger", "MergerBuilder", "Sorter", "SorterBuilder",
+           "lib", "LIB_PATH", "EXPORTS"]

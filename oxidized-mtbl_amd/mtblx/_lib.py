@@ -43,11 +43,13 @@ EXPORTS = [
     "mtblx_index_seek_batch", "mtblx_block_seek_batch", "mtblx_block_seek_batch_kbuf", "mtblx_block_seek_batch_ex", "mtblx_copy_ranges", "mtblx_entry_offsets",
     "mtblx_key_filter",
     "mtblx_merge_workspace_bytes", "mtblx_merge_plan", "mtblx_merge_emit", "mtblx_merge_plan_timed",
+    "mtblx_sort_workspace_bytes", "mtblx_sort_plan", "mtblx_sort_emit", "mtblx_sort_plan_timed",
 ]
 MERGE_MAX_SOURCES, MERGE_MAX_RECORDS = 64, (1 << 32) - 16
 MERGE_GROUPS, MERGE_CONCAT, MERGE_FIRST, MERGE_LAST = range(4)
 MERGE_UNSORTED, MERGE_INTERNAL = 1, 2          # totals[5] of mtblx_merge_plan
 MERGE_OVERFLOW, MERGE_NOT_PLANNED = 1, 2       # *flags of mtblx_merge_emit
+SORT_TILE = 1024                               # MTBLX_SORT_TILE: handles per tile-sorted run of mtblx_sort_plan
 PLAN_OUT_OF_ORDER, PLAN_PANIC, PLAN_TOO_LONG = 1, 2, 4
 
 
@@ -261,6 +263,15 @@ def lib() -> C.CDLL:
         L.mtblx_merge_emit.argtypes = [C.POINTER(Records), C.c_uint32, C.c_int, C.POINTER(Merged), C.c_void_p,
                                        C.c_size_t, C.c_void_p]
         L.mtblx_merge_emit.restype = C.c_int
+        L.mtblx_sort_workspace_bytes.argtypes = [C.c_uint64]
+        L.mtblx_sort_workspace_bytes.restype = C.c_size_t
+        L.mtblx_sort_plan.argtypes = [C.POINTER(Records), u64p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_sort_plan.restype = C.c_int
+        L.mtblx_sort_plan_timed.argtypes = L.mtblx_sort_plan.argtypes + [C.POINTER(C.c_float), C.c_uint32]
+        L.mtblx_sort_plan_timed.restype = C.c_int
+        L.mtblx_sort_emit.argtypes = [C.POINTER(Records), C.c_int, C.POINTER(Merged), C.c_void_p, C.c_size_t,
+                                      C.c_void_p]
+        L.mtblx_sort_emit.restype = C.c_int
         L.mtblx_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_uint64]
         L.mtblx_host_alloc.restype = C.c_int
         L.mtblx_host_free.argtypes = [C.c_void_p]
