@@ -451,6 +451,58 @@ int mtblx_encode_index(const mtblx_records* rec, const uint64_t* blk_rec, uint32
                        uint32_t restart_interval, const uint8_t* data, uint64_t region_off, uint64_t data_bytes,
                        const uint64_t* blk_off, const uint32_t* blk_len, uint8_t* file, uint64_t file_cap,
                        uint64_t* file_len, void* stream);
+/* mtblx_encode_index for data blocks stored with `compression` (the footer's
+ * compression_algorithm, src/metadata.rs:69: 0 None, 1 Snappy): the region holds the blocks
+ * framed as stored (mtblx_frame_blocks), blk_off/blk_len address the STORED contents, and
+ * data_bytes (bytes_data_blocks, the index block's offset) is the stored region's size.  The
+ * index block itself stays CompressionType::None (src/writer.rs:165-173).  mtblx_encode_index
+ * is this call with compression = 0. */
+int mtblx_encode_index_c(const mtblx_records* rec, const uint64_t* blk_rec, uint32_t nblk, uint64_t block_size,
+                         uint32_t restart_interval, const uint8_t* data, uint64_t region_off, uint64_t data_bytes,
+                         const uint64_t* blk_off, const uint32_t* blk_len, uint8_t* file, uint64_t file_cap,
+                         uint32_t compression, uint64_t* file_len, void* stream);
+
+/* ---- snappy raw compression on the device: the device Writer's CompressionType::Snappy ----
+ * write_block's compression step (src/writer.rs:213-214 -> src/compression.rs:126-130,
+ * snap::raw::Encoder::compress_vec) for a batch of blocks, and its framing of the stored bytes.
+ * Block b's uncompressed content is src[src_off[b] .. + src_len[b]) (device, any alignment);
+ * each is compressed on its own into a Snappy raw stream: varint32 length, literal, copy-1 and
+ * copy-2 elements (no copy-4), no match across a 64 KiB fragment boundary; src_len 0 gives the
+ * single byte 0x00.  The compressed bytes are valid Snappy that decodes to the block; they are
+ * not the host compressor's bytes (neither is pinned to the reference's).  Equal inputs give
+ * equal bytes, run after run.
+ *
+ * mtblx_snappy_slots: the output layout: dst_off[b] = the exclusive prefix of
+ * mtblx_snappy_max_compressed_len(src_len[b]) rounded up to 16 bytes; totals (device [1]) =
+ * the bytes the slots need.
+ *
+ * mtblx_snappy_compress_dev: block b's stream goes to dst[dst_off[b] .. + dst_len[b]).  Its
+ * slot ends at dst_off[b + 1] (dst_off non-decreasing; the last slot ends at dst_cap).
+ * status[b] = MTBLX_ST_OK, or MTBLX_ST_OVERFLOW when the slot is smaller than
+ * mtblx_snappy_max_compressed_len(src_len[b]) or runs past dst_cap: nothing is written for
+ * that block and dst_len[b] = 0.  {dst, dst_off, dst_len} is directly the input of
+ * mtblx_snappy_dir / mtblx_snappy_decompress_dev and of mtblx_frame_blocks.
+ *
+ * mtblx_frame_blocks: write_block's framing (src/writer.rs:203-237) over nblk stored contents:
+ * out = varint64(len) | crc32c(content) LE | content, back to back from out[0];
+ * blk_off[b] (device [nblk]) = the content's start in out; totals (device [2]) = bytes
+ * written, flags (bit 0: out_cap too small, the blocks that do not fit are not written).
+ * The checksums come from mtblx_crc32c_blocks' kernel, which reads whole aligned 16-byte
+ * chunks: up to 15 bytes around a range inside the aligned 16 bytes holding its ends.
+ * workspace: mtblx_snappy_compress_workspace_bytes(nblk) bytes (device, 4-byte aligned, no fill);
+ * nblk == 0 writes totals = {0, 0} and takes none (NULL allowed, as for the other two calls).
+ *
+ * All three are asynchronous on `stream`, keep no library-owned scratch and never synchronise
+ * with the host.  workspace may be NULL for the first two (they use none today). */
+size_t mtblx_snappy_compress_workspace_bytes(uint32_t nblk);
+int mtblx_snappy_slots(const uint32_t* src_len, uint32_t nblk, uint64_t* dst_off, uint64_t* totals, void* workspace,
+                       size_t ws_bytes, void* stream);
+int mtblx_snappy_compress_dev(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len, uint32_t nblk,
+                              uint8_t* dst, uint64_t dst_cap, const uint64_t* dst_off, uint32_t* dst_len,
+                              int32_t* status, void* workspace, size_t ws_bytes, void* stream);
+int mtblx_frame_blocks(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len, uint32_t nblk,
+                       uint8_t* out, uint64_t out_cap, uint64_t* blk_off, uint64_t* totals, void* workspace,
+                       size_t ws_bytes, void* stream);
 
 /* ---- Merger on the device: k-way merge of sorted sources, duplicate keys grouped (src/merger.rs) ----
  * nsrc sources (host array of mtblx_records with device pointers, keys strictly increasing within a

@@ -167,12 +167,13 @@ struct DevMem {   // temporaries of this (synchronous, once-per-file) call
 };
 }  // namespace
 
-extern "C" int mtblx_encode_index(const mtblx_records* rec, const uint64_t* blk_rec, uint32_t nblk,
-                                  uint64_t block_size, uint32_t restart_interval, const uint8_t* data,
-                                  uint64_t region_off, uint64_t data_bytes, const uint64_t* blk_off,
-                                  const uint32_t* blk_len, uint8_t* file, uint64_t file_cap, uint64_t* file_len,
-                                  void* stream) {
+extern "C" int mtblx_encode_index_c(const mtblx_records* rec, const uint64_t* blk_rec, uint32_t nblk,
+                                    uint64_t block_size, uint32_t restart_interval, const uint8_t* data,
+                                    uint64_t region_off, uint64_t data_bytes, const uint64_t* blk_off,
+                                    const uint32_t* blk_len, uint8_t* file, uint64_t file_cap, uint32_t compression,
+                                    uint64_t* file_len, void* stream) {
   using namespace mtblx_idx;
+  if (compression > 5) return MTBLX_E_INVAL;   // CompressionType (src/compression.rs:6-15)
   if (!rec || !file || !file_len || (nblk && (!blk_rec || !blk_off || !blk_len || !data))) return MTBLX_E_INVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (block_size < 1024) block_size = 1024;   // WriterBuilder::block_size clamp (src/writer.rs:43-46)
@@ -236,7 +237,7 @@ extern "C" int mtblx_encode_index(const mtblx_records* rec, const uint64_t* blk_
   }
   uint8_t foot[512];
   memset(foot, 0, sizeof foot);
-  const uint64_t meta[9] = {data_bytes, block_size, 0, r1 - r0, nblk, data_bytes, idx_bytes, k1 - k0, v1 - v0};
+  const uint64_t meta[9] = {data_bytes, block_size, compression, r1 - r0, nblk, data_bytes, idx_bytes, k1 - k0, v1 - v0};
   memcpy(foot, meta, sizeof meta);   // little-endian host (x86-64)
   const uint32_t magic = 0x4D54424Cu;   // FormatV2 (src/lib.rs:17-20)
   memcpy(foot + 508, &magic, 4);
@@ -245,4 +246,13 @@ extern "C" int mtblx_encode_index(const mtblx_records* rec, const uint64_t* blk_
     return MTBLX_E_HIP;
   *file_len = data_bytes + idx_bytes + 512;
   return MTBLX_OK;
+}
+
+extern "C" int mtblx_encode_index(const mtblx_records* rec, const uint64_t* blk_rec, uint32_t nblk,
+                                  uint64_t block_size, uint32_t restart_interval, const uint8_t* data,
+                                  uint64_t region_off, uint64_t data_bytes, const uint64_t* blk_off,
+                                  const uint32_t* blk_len, uint8_t* file, uint64_t file_cap, uint64_t* file_len,
+                                  void* stream) {
+  return mtblx_encode_index_c(rec, blk_rec, nblk, block_size, restart_interval, data, region_off, data_bytes, blk_off,
+                              blk_len, file, file_cap, 0, file_len, stream);
 }

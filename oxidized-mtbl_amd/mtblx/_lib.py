@@ -44,6 +44,8 @@ EXPORTS = [
     "mtblx_key_filter",
     "mtblx_merge_workspace_bytes", "mtblx_merge_plan", "mtblx_merge_emit", "mtblx_merge_plan_timed",
     "mtblx_sort_workspace_bytes", "mtblx_sort_plan", "mtblx_sort_emit", "mtblx_sort_plan_timed",
+    "mtblx_snappy_compress_workspace_bytes", "mtblx_snappy_slots", "mtblx_snappy_compress_dev", "mtblx_frame_blocks",
+    "mtblx_encode_index_c",
 ]
 MERGE_MAX_SOURCES, MERGE_MAX_RECORDS = 64, (1 << 32) - 16
 MERGE_GROUPS, MERGE_CONCAT, MERGE_FIRST, MERGE_LAST = range(4)
@@ -220,6 +222,19 @@ def lib() -> C.CDLL:
                                          C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p,
                                          C.c_void_p]
         L.mtblx_encode_index.restype = C.c_int
+        L.mtblx_encode_index_c.argtypes = L.mtblx_encode_index.argtypes[:-2] + [C.c_uint32, u64p, C.c_void_p]
+        L.mtblx_encode_index_c.restype = C.c_int
+        L.mtblx_snappy_compress_workspace_bytes.argtypes = [C.c_uint32]
+        L.mtblx_snappy_compress_workspace_bytes.restype = C.c_size_t
+        L.mtblx_snappy_slots.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]
+        L.mtblx_snappy_slots.restype = C.c_int
+        L.mtblx_snappy_compress_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_snappy_compress_dev.restype = C.c_int
+        L.mtblx_frame_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_frame_blocks.restype = C.c_int
         L.mtblx_codec_available.argtypes = [C.c_uint32]
         L.mtblx_codec_available.restype = C.c_int
         L.mtblx_decompress.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(u8p), u64p]

@@ -407,3 +407,63 @@ def snappy_decompress(batch: SnappyBatch, stream=None):
     snappy_decompress_into(batch, lay, dst, status, dec_len, mx, stream)
     out = DeviceBatch(dst, lay.dst_off[: batch.nblk], dec_len[: batch.nblk], mx)
     return out, status[: batch.nblk]
+
+
+# ---------------- snappy raw compression on the device (the device Writer's Snappy) ----------------
+class SnappySlots:
+    """Output layout of a batch to compress (mtblx_snappy_slots): dst_off (16-byte aligned
+    slots of mtblx_snappy_max_compressed_len bytes), totals[0] = the bytes the slots need, and
+    the workspace the compress / frame calls take."""
+
+    def __init__(self, nblk: int, device="cuda"):
+        n = max(nblk, 1)
+        self.nblk = nblk
+        self.dst_off = torch.zeros(n, dtype=torch.int64, device=device)
+        self.totals = torch.zeros(2, dtype=torch.int64, device=device)
+        self.ws_bytes = int(_lib.lib().mtblx_snappy_compress_workspace_bytes(nblk))
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
+
+
+def snappy_slots(batch: DeviceBatch, slots: SnappySlots, stream=None) -> None:
+    L = _require_device()
+    rc = L.mtblx_snappy_slots(C.c_void_p(_u(batch.blk_len)), batch.nblk, C.c_void_p(_u(slots.dst_off)),
+                              C.c_void_p(_u(slots.totals)), C.c_void_p(_u(slots.ws)), slots.ws_bytes,
+                              C.c_void_p(_stream_handle(stream)))
+    if rc != 0:
+        raise RuntimeError(f"mtblx_snappy_slots failed: {rc}")
+
+
+def snappy_compress_into(batch: DeviceBatch, slots: SnappySlots, dst: torch.Tensor, dst_len: torch.Tensor,
+                         status: torch.Tensor, stream=None) -> None:
+    """Asynchronous device compression of every block into dst at slots.dst_off (mtblx_snappy_compress_dev)."""
+    L = _require_device()
+    rc = L.mtblx_snappy_compress_dev(C.c_void_p(_u(batch.data)), C.c_void_p(_u(batch.blk_off)),
+                                     C.c_void_p(_u(batch.blk_len)), batch.nblk, C.c_void_p(_u(dst)), int(dst.numel()),
+                                     C.c_void_p(_u(slots.dst_off)), C.c_void_p(_u(dst_len)), C.c_void_p(_u(status)),
+                                     C.c_void_p(_u(slots.ws)), slots.ws_bytes, C.c_void_p(_stream_handle(stream)))
+    if rc != 0:
+        raise RuntimeError(f"mtblx_snappy_compress_dev failed: {rc}")
+
+
+def snappy_compress(batch: DeviceBatch, stream=None):
+    """Slots + compress -> (SnappyBatch of the compressed blocks, status int32 [nblk]): the
+    block-level counterpart of snappy_decompress.  Each block becomes a Snappy raw stream in its
+    own 16-byte aligned slot; status is MTBLX_ST_OK per block (slots sized here always fit).
+    Synchronises for the slots' size (and, with a `stream`, around its own buffer fills); the
+    compression itself is left running on `stream`."""
+    _require_device()
+    dev = batch.data.device
+    slots = SnappySlots(batch.nblk, dev)
+    if stream is not None:   # the zero fills of a fresh buffer run on the current stream, the kernels on `stream`
+        torch.cuda.synchronize()
+    snappy_slots(batch, slots, stream)
+    torch.cuda.synchronize()
+    total = int(slots.totals[0].item())
+    dst = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+    n = max(batch.nblk, 1)
+    dst_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    if stream is not None:
+        torch.cuda.synchronize()
+    snappy_compress_into(batch, slots, dst, dst_len, status, stream)
+    return SnappyBatch(dst, slots.dst_off[: batch.nblk], dst_len[: batch.nblk]), status[: batch.nblk]

@@ -15,6 +15,7 @@ import torch
 
 from . import _lib, codec
 from ._lib import Records
+from .writer import CompressionType
 
 
 class WriterPanic(RuntimeError):
@@ -192,11 +193,20 @@ def encode_blocks(recs: DeviceRecords, blk_rec: torch.Tensor, restart_interval: 
     return encode_into(recs, blk_rec, bufs, restart_interval, framed, stream, plan)
 
 
-def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: int = 16, stream=None) -> torch.Tensor:
+def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: int = 16, stream=None,
+               compression: int = CompressionType.None_) -> torch.Tensor:
     """The crate's Writer on the device for ONE file (src/writer.rs): insert every record
-    (block cut: plan; BlockBuilder + write_block: encode_blocks, framed), then into_inner
-    (index block + footer: mtblx_encode_index).  -> the file bytes (device uint8), byte-identical
-    to Writer::into_inner for the same records (CompressionType::None)."""
+    (block cut: plan; BlockBuilder + write_block: encode_blocks), then into_inner (index block +
+    footer: mtblx_encode_index_c).  -> the file bytes (device uint8).
+    compression None_: blocks framed as built; byte-identical to Writer::into_inner for the same
+    records.  Snappy: the blocks are built unframed, compressed on the device
+    (mtblx_snappy_compress_dev) and framed as stored (mtblx_frame_blocks); every block
+    decompresses to the None file's block, the compressed bytes themselves are this library's
+    (valid Snappy, not pinned to any other compressor's).  Other types are host-only."""
+    compression = int(compression)
+    if compression not in (CompressionType.None_, CompressionType.Snappy):
+        raise ValueError(f"write_file: compression {compression} is not available on the device (None and Snappy "
+                         f"are); for zlib and zstd use the host path, write_into(Writer(compression=...))")
     L = codec._require_device()
     dev = recs.key_end.device
     kept = None
@@ -209,8 +219,9 @@ def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: in
         blk = plan(recs, block_size, restart_interval, stream=stream)
     nblk = int(blk.numel()) - 1
     kbytes = int(recs.key_end[-1].item()) if recs.n else 0
+    snappy = compression == CompressionType.Snappy
     if nblk:
-        e = encode_blocks(recs, blk, restart_interval, framed=True, stream=stream, plan=kept)
+        e = encode_blocks(recs, blk, restart_interval, framed=not snappy, stream=stream, plan=kept)
         torch.cuda.synchronize()
         e.check()
         if int(e.totals[1].item()) & 1:
@@ -221,15 +232,44 @@ def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: in
         data_bytes = 0
         data = off = ln = None
     # index block: separators (<= last key + 2 B) + varint64 offsets + headers + restarts + framing
-    cap = data_bytes + kbytes + 36 * nblk + 64 + 512
-    file = torch.empty(cap, dtype=torch.uint8, device=dev)
+    tail = kbytes + 36 * nblk + 64 + 512
+    if snappy and nblk:
+        comp, cst = codec.snappy_compress(e.batch(), stream=stream)
+        torch.cuda.synchronize()   # the kernels ran on `stream`; the reads below are on the current stream
+        stored = int(comp.src_len.sum().item())   # synchronises: the compressed sizes size the file
+        if bool((cst != 0).any()):
+            raise RuntimeError("mtblx_snappy_compress_dev: a block did not fit its slot")
+        del e, data   # the raw contents are not needed any more
+        cap = stored + 14 * nblk + tail   # framing: varint64(len) <= 10 bytes + 4 of checksum per block
+        file = torch.empty(cap, dtype=torch.uint8, device=dev)
+        off = torch.empty(nblk, dtype=torch.int64, device=dev)
+        ftot = torch.zeros(2, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()   # ftot's fill (current stream) before k_len_scan writes it on `stream`
+        wsb = int(L.mtblx_snappy_compress_workspace_bytes(nblk))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        u = codec._u
+        rc = L.mtblx_frame_blocks(C.c_void_p(u(comp.data)), C.c_void_p(u(comp.src_off)), C.c_void_p(u(comp.src_len)),
+                                  nblk, C.c_void_p(file.data_ptr()), cap - tail, C.c_void_p(u(off)),
+                                  C.c_void_p(u(ftot)), C.c_void_p(u(ws)), wsb,
+                                  C.c_void_p(codec._stream_handle(stream)))
+        if rc != 0:
+            raise RuntimeError(f"mtblx_frame_blocks failed: {rc}")
+        torch.cuda.synchronize()
+        data_bytes, fflags = (int(x) for x in ftot.tolist())
+        if fflags & 1:
+            raise RuntimeError("mtblx_frame_blocks: the framed blocks did not fit")
+        data, ln = file, comp.src_len
+    else:
+        cap = data_bytes + tail
+        file = torch.empty(cap, dtype=torch.uint8, device=dev)
     n = C.c_uint64(0)
     rc_ = recs.cstruct()
     u = codec._u
-    rc = L.mtblx_encode_index(C.byref(rc_), C.c_void_p(u(blk)), nblk, int(block_size), int(restart_interval),
-                              C.c_void_p(u(data) if data is not None else u(file)), 0, data_bytes,
-                              C.c_void_p(u(off) if off is not None else 0), C.c_void_p(u(ln) if ln is not None else 0),
-                              C.c_void_p(file.data_ptr()), cap, C.byref(n), C.c_void_p(codec._stream_handle(stream)))
+    rc = L.mtblx_encode_index_c(C.byref(rc_), C.c_void_p(u(blk)), nblk, int(block_size), int(restart_interval),
+                                C.c_void_p(u(data) if data is not None else u(file)), 0, data_bytes,
+                                C.c_void_p(u(off) if off is not None else 0), C.c_void_p(u(ln) if ln is not None else 0),
+                                C.c_void_p(file.data_ptr()), cap, compression, C.byref(n),
+                                C.c_void_p(codec._stream_handle(stream)))
     if rc == _lib.MTBLX_E_TIMEOUT:
         raise codec.LaunchTimeout("mtblx_encode_index: look-back timeout")
     if rc != 0:

@@ -28,6 +28,7 @@ import torch
 
 from . import _lib, codec, encode
 from .encode import DeviceRecords
+from .writer import CompressionType
 
 MODES = {"groups": _lib.MERGE_GROUPS, "concat": _lib.MERGE_CONCAT, "first": _lib.MERGE_FIRST,
          "last": _lib.MERGE_LAST}
@@ -245,9 +246,11 @@ class Merger:
             return DeviceRecords.from_list(self._merged_list(), device=self._device() or "cuda")
         return self._run(self.merge)
 
-    def write_file(self, block_size: int = 8192, restart_interval: int = 16) -> torch.Tensor:
+    def write_file(self, block_size: int = 8192, restart_interval: int = 16,
+                   compression: int = CompressionType.None_) -> torch.Tensor:
         """the merged .mtbl file (device uint8), written by the device Writer"""
-        return encode.write_file(self.records(), block_size, restart_interval, stream=self.stream)
+        return encode.write_file(self.records(), block_size, restart_interval, stream=self.stream,
+                                 compression=compression)
 
     def write_into(self, writer) -> None:
         """Merger::write_into (src/merger.rs:149-156) for the host Writer"""

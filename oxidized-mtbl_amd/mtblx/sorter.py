@@ -290,9 +290,11 @@ class Sorter:
         """MergerIter over the chunks: (key, merged value) per distinct key"""
         return iter(_records_list(self.records()))
 
-    def write_file(self, block_size: int = 8192, restart_interval: int = 16) -> torch.Tensor:
+    def write_file(self, block_size: int = 8192, restart_interval: int = 16,
+                   compression: int = CompressionType.None_) -> torch.Tensor:
         """the .mtbl file (device uint8), written by the device Writer"""
-        return encode.write_file(self.records(), block_size, restart_interval, stream=self.stream)
+        return encode.write_file(self.records(), block_size, restart_interval, stream=self.stream,
+                                 compression=compression)
 
     def write_into(self, writer) -> None:
         """Sorter::write_into (:235-242) for the host Writer"""
