@@ -1,12 +1,15 @@
-// decode.hip — MI355X (gfx950) kernel for mtbl data-block decode.
+// decode.hip — MI355X (gfx950) kernels for mtbl data-block decode.
 //
 // Replaces the reference's per-record CPU scan of one block
-//   Block::init            /root/reference/src/block.rs:16-49
+//   Block::init            src/block.rs:16-49
 //   BlockIter::init        src/block.rs:75-93
 //   seek_to_first / next / get / parse_next_key / decode_entry   src/block.rs:119-238
 //   varint_decode32        src/varint.rs:44-61
 // with ONE single-pass launch over a batch of blocks, output laid out contiguously
-// (include/mtblx.h).  See k_decode_tiles below and DESIGN.md "Kernels".
+// (include/mtblx.h).  The main kernel is k_decode_pipe (a persistent, wave-specialised pipeline:
+// LDS-DMA loaders, a walker, a look-back wave and copy waves; make_plan picks its configuration
+// from the batch's largest block); k_decode_tiles takes the batches whose largest block fits no
+// pipeline stage.  See DESIGN.md "Kernels".
 //
 // Everything is integer/byte work: HBM-bandwidth bound (the fused verify's CRC is VALU slicing
 // here; the separate-launch CRC, crc.hip, runs it on the matrix cores).
@@ -20,14 +23,12 @@
 #include "bounds.h"
 #include "devinfo.h"
 #include "crc_dev.h"
-#include "crc_mfma.h"
-#include "crc_mfma_dev.h"
 #include "mtblx.h"
 
 // Ablations (outputs incomplete by construction) and the spilling variant build only through the
 // Makefile's diagnostic targets, which define MTBLX_DIAG; the product build rejects them.
 #if (defined(MTBLX_ABL_NOKEY) || defined(MTBLX_ABL_NOVAL) || defined(MTBLX_ABL_NOVSTORE) || \
-     defined(MTBLX_ABL_CRC) || defined(MTBLX_SPILL) || defined(MTBLX_CALL_PROBE)) && !defined(MTBLX_DIAG)
+     defined(MTBLX_ABL_CRC) || defined(MTBLX_SPILL)) && !defined(MTBLX_DIAG)
 #error "ablation / spill knobs are diagnostic: build them through a Makefile diagnostic target (-DMTBLX_DIAG)"
 #endif
 
@@ -96,33 +97,16 @@ typedef uint32_t __attribute__((aligned(1))) u32u;
 typedef uint16_t __attribute__((aligned(1))) u16u;
 
 // Output stores.  The decoded keys / values / ends are written once and never read back by
-// this launch: non-temporal stores (MTBLX_NT_STORES) stream them out instead of leaving the
-// XCD L2s full of dirty lines that the end-of-launch release must write back.
-#ifndef MTBLX_NT_STORES
-#define MTBLX_NT_STORES 2
-#endif
+// this launch: non-temporal stores stream them out instead of leaving the XCD L2s full of dirty
+// lines that the end-of-launch release must write back.
+#define ost(p, ...) (MTBLX_CHK((p), sizeof(*(p))), __builtin_nontemporal_store((__VA_ARGS__), (p)))
+// byte-granular stores (keys of any length, value tails) stay in L2, where partial lines merge
+// before they are written back
+#define ostb(p, ...) (void)(*(p) = (__VA_ARGS__))
 // LDS-DMA of the block bytes with the non-temporal policy (aux = 2): the blocks are read once, so
 // they stay out of the L2s the byte-granular key stores merge in (cfg2 +5 %, 64 KiB +4 %)
 #ifndef MTBLX_DMA_AUX   // cache-policy bits of the LDS-DMA loads (2 = non-temporal)
 #define MTBLX_DMA_AUX 2
-#endif
-#ifndef MTBLX_NT_LOADS
-#define MTBLX_NT_LOADS 1
-#endif
-#ifndef MTBLX_WSEND_LIGHT
-#define MTBLX_WSEND_LIGHT 1
-#endif
-#if MTBLX_NT_STORES
-#define ost(p, ...) (MTBLX_CHK((p), sizeof(*(p))), __builtin_nontemporal_store((__VA_ARGS__), (p)))
-#else
-#define ost(p, ...) (MTBLX_CHK((p), sizeof(*(p))), (void)(*(p) = (__VA_ARGS__)))
-#endif
-// byte-granular stores (keys of any length, value tails): MTBLX_NT_STORES == 1 streams them
-// too; == 2 keeps them in L2, where partial lines merge before they are written back
-#if MTBLX_NT_STORES == 1
-#define ostb(p, ...) __builtin_nontemporal_store((__VA_ARGS__), (p))
-#else
-#define ostb(p, ...) (void)(*(p) = (__VA_ARGS__))
 #endif
 
 // store the first m (0..16) bytes of w at p
@@ -307,8 +291,7 @@ __device__ __forceinline__ bool gen_writable(uint32_t bo, int32_t st) {
 // one workgroup (256 threads).  Workgroups are persistent and take tiles t = blockIdx.x,
 // + G, + 2G ... (G = gridDim.x, never more than the resident capacity).
 // Per tile:
-//   stage (from registers prefetched during the previous tile) -> prefetch the next tile
-//   -> trailers -> walk 1 (one thread per restart interval across the tile, counts)
+//   stage -> trailers -> walk 1 (one thread per restart interval across the tile, counts)
 //   -> interval scan -> publish the tile aggregate -> issue the look-back loads
 //   -> walk 2 (per-record metadata into LDS, hides the look-back latency)
 //   -> finish the look-back -> per-block outputs -> copy (one thread per record)
@@ -324,16 +307,14 @@ constexpr int kThreads = 256;
 constexpr int kMaxLookbackLoads = 4;               // G - 1 <= 4 * 256
 constexpr uint64_t kReady = 1ull << 63;
 constexpr uint32_t kField = (1u << 21) - 1;        // 21-bit fields: nrec | vbytes | kbytes
-constexpr int kPrefetch = 8;                       // uint4 per thread prefetched (32 KiB tiles)
 
-template <int TB_, int MAXREC_, int MAXINT_, int MAXBLK_, bool PREFETCH_, int MINW_>
+template <int TB_, int MAXREC_, int MAXINT_, int MAXBLK_, int MINW_>
 struct TileCfg {
   static constexpr int MINW = MINW_;     // workgroups per CU to keep resident (__launch_bounds__)
   static constexpr int TB = TB_;          // staging bytes
   static constexpr int MAXREC = MAXREC_;  // records with metadata per chunk
   static constexpr int MAXINT = MAXINT_;  // restart intervals per tile (<= kThreads)
   static constexpr int MAXBLK = MAXBLK_;  // blocks per tile (<= 64)
-  static constexpr bool PREFETCH = PREFETCH_;
   static constexpr bool VALPOS = false;   // positions mode: val_pos instead of value bytes (CfgLargeP)
 };
 
@@ -520,16 +501,11 @@ struct WaitBound {
 __device__ __forceinline__ void ws_end(const TileArgs& a) {
   __syncthreads();
   if (threadIdx.x == 0) {
-#if MTBLX_WSEND_LIGHT
     // What the last workgroup reads from the others is only `flags`, which they update with
     // agent-scope atomics; the __syncthreads above waited (vmcnt) until this workgroup's were
     // performed.  No agent-scope release: on gfx950 it writes back the XCD's whole L2
     // (buffer_wbl2), i.e. every dirty output line, once per workgroup.
     const uint32_t old = __hip_atomic_fetch_add(&a.hdr->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    const uint32_t old = __hip_atomic_fetch_add(&a.hdr->done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-#endif
     if (old == gridDim.x - 1) {
       const unsigned long long f = __hip_atomic_exchange(&a.hdr->flags, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       a.totals[3] = f | a.inject;
@@ -584,7 +560,7 @@ __device__ __forceinline__ void tile_range(const TileArgs& a, uint32_t t, uint32
     if (a.blk_off[b0 + j] < s || a.blk_off[b0 + j] + a.blk_len[b0 + j] > e) r1 = 0;
 }
 
-// prefetch chunk c (16 B) of a contiguous range into v (zero-filled outside the buffer)
+// the 16 bytes at `off` of the data buffer (zero-filled outside the buffer)
 __device__ __forceinline__ uint4 load_chunk(const TileArgs& a, uint64_t off) {
   if (off + 16 <= a.data_len) {
     MTBLX_CHK(a.data + off, 16);
@@ -782,20 +758,6 @@ __global__ void __launch_bounds__(kThreads, C::MINW) k_decode_tiles(TileArgs a) 
 #endif
   if (tid == 0) { S.tinc[0] = S.tinc[1] = S.tinc[2] = 0; }
 
-  // prefetch registers for the next tile's contiguous range
-  uint4 pf[kPrefetch];
-  uint64_t pr0 = 0, pr1 = 0;
-  if (C::PREFETCH && blockIdx.x < a.ntiles) {
-    tile_range(a, blockIdx.x, C::TB, pr0, pr1);
-    if (pr1) {
-#pragma unroll
-      for (int k = 0; k < kPrefetch; ++k) {
-        const uint64_t o = pr0 + 16ull * (tid + k * kThreads);
-        pf[k] = (o < pr1) ? load_chunk(a, o) : make_uint4(0, 0, 0, 0);
-      }
-    }
-  }
-
   for (uint32_t t = blockIdx.x; t < a.ntiles; t += G) {
     uint32_t b0, nb;
     tile_span(a, t, b0, nb);
@@ -805,31 +767,21 @@ __global__ void __launch_bounds__(kThreads, C::MINW) k_decode_tiles(TileArgs a) 
     STAMP(7);
 
     // ---- 1. stage ----
-    uint64_t r0 = pr0, r1 = pr1;
-    if (!C::PREFETCH) tile_range(a, t, C::TB, r0, r1);
+    uint64_t r0, r1;
+    tile_range(a, t, C::TB, r0, r1);
     if (r1) {
       // contiguous layout: range byte x at stage offset 16 + x
       const uint32_t nch = (uint32_t)((r1 - r0 + 15) >> 4);
-      if (C::PREFETCH) {
+      constexpr int U = 4;
+      uint32_t c = tid;
+      for (; c + (U - 1) * kThreads < nch; c += U * kThreads) {
+        uint4 v[U];
 #pragma unroll
-        for (int k = 0; k < kPrefetch; ++k) {
-          const uint32_t c = tid + k * kThreads;
-          if (c < nch) *reinterpret_cast<uint4*>(S.stage + 16 + 16 * c) = pf[k];
-        }
-        for (uint32_t c = tid + kPrefetch * kThreads; c < nch; c += kThreads)
-          *reinterpret_cast<uint4*>(S.stage + 16 + 16 * c) = load_chunk(a, r0 + 16ull * c);
-      } else {
-        constexpr int U = 4;
-        uint32_t c = tid;
-        for (; c + (U - 1) * kThreads < nch; c += U * kThreads) {
-          uint4 v[U];
+        for (int u = 0; u < U; ++u) v[u] = load_chunk(a, r0 + 16ull * (c + u * kThreads));
 #pragma unroll
-          for (int u = 0; u < U; ++u) v[u] = load_chunk(a, r0 + 16ull * (c + u * kThreads));
-#pragma unroll
-          for (int u = 0; u < U; ++u) *reinterpret_cast<uint4*>(S.stage + 16 + 16 * (c + u * kThreads)) = v[u];
-        }
-        for (; c < nch; c += kThreads) *reinterpret_cast<uint4*>(S.stage + 16 + 16 * c) = load_chunk(a, r0 + 16ull * c);
+        for (int u = 0; u < U; ++u) *reinterpret_cast<uint4*>(S.stage + 16 + 16 * (c + u * kThreads)) = v[u];
       }
+      for (; c < nch; c += kThreads) *reinterpret_cast<uint4*>(S.stage + 16 + 16 * c) = load_chunk(a, r0 + 16ull * c);
       if (tid < (int)nb) {
         MTBLX_CHK(a.blk_off + b0 + tid, 8);
         MTBLX_CHK(a.blk_len + b0 + tid, 4);
@@ -855,21 +807,6 @@ __global__ void __launch_bounds__(kThreads, C::MINW) k_decode_tiles(TileArgs a) 
     }
     __syncthreads();
     STAMP(0);
-
-    // ---- 1b. prefetch the next tile of this workgroup into registers ----
-    if (C::PREFETCH) {
-      pr1 = 0;
-      if (t + G < a.ntiles) {
-        tile_range(a, t + G, C::TB, pr0, pr1);
-        if (pr1) {
-#pragma unroll
-          for (int k = 0; k < kPrefetch; ++k) {
-            const uint64_t o = pr0 + 16ull * (tid + k * kThreads);
-            pf[k] = (o < pr1) ? load_chunk(a, o) : make_uint4(0, 0, 0, 0);
-          }
-        }
-      }
-    }
 
     // ---- 2. trailers (Block::init, src/block.rs:16-49) + interval numbering (wave 0) ----
     if (wv == 0) {
@@ -1413,87 +1350,50 @@ __device__ __forceinline__ bool walk_pos(const uint8_t* stage, uint16_t* pos, ui
 // exact walk_careful_pos) any varint of 3+ bytes, shared > previous key length, an overshoot
 // or more than 16 entries.  Reads past R land inside the LDS allocation or return 0 and are
 // never used when the walk is rejected (p is monotonic; the result requires p == e <= R).
-#ifndef MTBLX_WALK2D   // 1: the instruction-lean walk below (+1.7 % on cfg3's decode, round 5); 0: round 4's
-#define MTBLX_WALK2D 1
-#endif
 __device__ __forceinline__ bool walk_pos2(const uint8_t* stage, uint16_t* pos, uint32_t bo, uint32_t s, uint32_t e,
                                           uint32_t slot0, uint32_t& cnt, uint32_t& kb, uint32_t& vb, bool& all1) {
   cnt = kb = vb = 0;
   all1 = false;
   if (!(s < e)) return false;
-#if MTBLX_WALK2D
-  // fewer instructions per entry on the serial chain: each varint's start from its predecessor's
+  // few instructions per entry on the serial chain (47 VALU, +1.7 % on cfg3's decode against a
+  // loop that shifts the window past one varint at a time): each varint's start from its predecessor's
   // continuation bit as a 64-bit shift of the window, its value by mask-and-merge, and the checks
   // folded into accumulators -- bit 15 of y & (y << 8) (the first two bytes of a varint both
   // continue: 3+ bytes), the sign of prevlen - shared (shared > the previous key's length)
-  {
-    uint32_t p = s, prevlen = 0, chk = 0, dsh = 0, any2 = 0, kbs = 0, vbs = 0, c = 0;
-    const uint32_t* st32 = reinterpret_cast<const uint32_t*>(stage);
-    do {
-      const uint32_t ad = bo + p, q = ad >> 2, sft = (ad & 3u) * 8u;
-      MTBLX_LCHK(st32 + q, 12);
-      const uint32_t w0 = st32[q], w1 = st32[q + 1], w2 = st32[q + 2];
-      const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, sft), hi = __builtin_amdgcn_alignbit(w2, w1, sft);
-      const uint64_t x = ((uint64_t)hi << 32) | lo;
-      const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe((int)lo, 7, 1);   // 0 or ~0: 2-byte varint
-      const uint32_t s1 = 8u + (m0 & 8u);                                     // bits to varint 1
-      const uint32_t y1 = (uint32_t)(x >> s1);
-      const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int)y1, 7, 1);
-      const uint32_t s2 = s1 + 8u + (m1 & 8u);
-      const uint32_t y2 = (uint32_t)(x >> s2);
-      const uint32_t m2 = (uint32_t)__builtin_amdgcn_sbfe((int)y2, 7, 1);
-      const uint32_t hl = (s2 >> 3) + 1u + (m2 & 1u);
-      const uint32_t f0 = (lo & 0x7fu) | ((lo >> 1) & 0x3f80u & m0);
-      const uint32_t f1 = (y1 & 0x7fu) | ((y1 >> 1) & 0x3f80u & m1);
-      const uint32_t f2 = (y2 & 0x7fu) | ((y2 >> 1) & 0x3f80u & m2);
-      chk |= (lo & (lo << 8)) | (y1 & (y1 << 8)) | (y2 & (y2 << 8));
-      any2 |= m0 | m1 | m2;
-      pos[slot0 + c] = (uint16_t)p;
-      dsh |= prevlen - f0;
-      prevlen = f0 + f1;
-      kbs += prevlen;
-      vbs += f2;
-      c += 1;
-      p += hl + f1 + f2;
-    } while (p < e && c < (uint32_t)kP2Spi);
-    cnt = c;
-    vb = vbs;
-    kb = kbs;
-    all1 = any2 == 0u;   // every header 1-byte varints: walk_pos would have accepted it
-    return p == e && (chk & 0x8000u) == 0u && (dsh >> 31) == 0u;
-  }
-#endif
-  uint32_t p = s, prevlen = 0, bad = 0, ssh = 0, svl = 0, shl = 0, c = 0;
+  uint32_t p = s, prevlen = 0, chk = 0, dsh = 0, any2 = 0, kbs = 0, vbs = 0, c = 0;
   const uint32_t* st32 = reinterpret_cast<const uint32_t*>(stage);
   do {
     const uint32_t ad = bo + p, q = ad >> 2, sft = (ad & 3u) * 8u;
     MTBLX_LCHK(st32 + q, 12);
     const uint32_t w0 = st32[q], w1 = st32[q + 1], w2 = st32[q + 2];
-    uint64_t x = (uint64_t)__builtin_amdgcn_alignbit(w1, w0, sft) |
-                 ((uint64_t)__builtin_amdgcn_alignbit(w2, w1, sft) << 32);
-    uint32_t f[3], hl = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const uint32_t b0 = (uint32_t)x & 0xffu, b1 = (uint32_t)(x >> 8) & 0xffu, two = b0 >> 7;
-      f[k] = (b0 & 0x7fu) | (two ? (b1 & 0x7fu) << 7 : 0u);
-      bad |= two & (b1 >> 7);                    // a 3+ byte varint
-      x >>= 8u * (1u + two);
-      hl += 1u + two;
-    }
+    const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, sft), hi = __builtin_amdgcn_alignbit(w2, w1, sft);
+    const uint64_t x = ((uint64_t)hi << 32) | lo;
+    const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe((int)lo, 7, 1);   // 0 or ~0: 2-byte varint
+    const uint32_t s1 = 8u + (m0 & 8u);                                     // bits to varint 1
+    const uint32_t y1 = (uint32_t)(x >> s1);
+    const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int)y1, 7, 1);
+    const uint32_t s2 = s1 + 8u + (m1 & 8u);
+    const uint32_t y2 = (uint32_t)(x >> s2);
+    const uint32_t m2 = (uint32_t)__builtin_amdgcn_sbfe((int)y2, 7, 1);
+    const uint32_t hl = (s2 >> 3) + 1u + (m2 & 1u);
+    const uint32_t f0 = (lo & 0x7fu) | ((lo >> 1) & 0x3f80u & m0);
+    const uint32_t f1 = (y1 & 0x7fu) | ((y1 >> 1) & 0x3f80u & m1);
+    const uint32_t f2 = (y2 & 0x7fu) | ((y2 >> 1) & 0x3f80u & m2);
+    chk |= (lo & (lo << 8)) | (y1 & (y1 << 8)) | (y2 & (y2 << 8));
+    any2 |= m0 | m1 | m2;
     pos[slot0 + c] = (uint16_t)p;
-    bad |= (uint32_t)(f[0] > prevlen);
-    prevlen = f[0] + f[1];
-    ssh += f[0];
-    svl += f[2];
-    shl += hl;
+    dsh |= prevlen - f0;
+    prevlen = f0 + f1;
+    kbs += prevlen;
+    vbs += f2;
     c += 1;
-    p += hl + f[1] + f[2];
+    p += hl + f1 + f2;
   } while (p < e && c < (uint32_t)kP2Spi);
   cnt = c;
-  vb = svl;
-  kb = ssh + (p - s) - shl - svl;   // sum(shared + non_shared): p - s = sum(header + ns + vl)
-  all1 = shl == 3u * c;             // every header 1-byte varints: walk_pos would have accepted it
-  return p == e && bad == 0u;
+  vb = vbs;
+  kb = kbs;
+  all1 = any2 == 0u;   // every header 1-byte varints: walk_pos would have accepted it
+  return p == e && (chk & 0x8000u) == 0u && (dsh >> 31) == 0u;
 }
 
 // exact walk (multi-byte varint headers allowed) recording header offsets; same checks as
@@ -1572,12 +1472,12 @@ __device__ __forceinline__ void pipe_dma(PipeBuf<P>& B, const TileArgs& a, uint3
     if (mlo <= part) m = part;
     const uint8_t* gp = a.data + r0 + 16ull * ((uint64_t)m * kWave + (uint32_t)lane);
     for (; m < mfull; m += P::LOADW, gp += 16 * kWave * P::LOADW)
-      MTBLX_CHK(gp, 16), MTBLX_LCHK(B.stage + 16 + 1024 * m, 1024), __builtin_amdgcn_global_load_lds((g_void*)gp, (lds_void*)(B.stage + 16 + 1024 * m), 16, 0, MTBLX_NT_LOADS ? MTBLX_DMA_AUX : 0);
+      MTBLX_CHK(gp, 16), MTBLX_LCHK(B.stage + 16 + 1024 * m, 1024), __builtin_amdgcn_global_load_lds((g_void*)gp, (lds_void*)(B.stage + 16 + 1024 * m), 16, 0, MTBLX_DMA_AUX);
     for (; m * kWave < nch && m < mhi; m += P::LOADW) {
       const uint32_t c = m * kWave + lane;
       const uint64_t go = r0 + 16ull * c;
       if (c < nfull)
-        MTBLX_CHK(a.data + go, 16), MTBLX_LCHK(B.stage + 16 + 1024 * m, 1024), __builtin_amdgcn_global_load_lds((g_void*)(a.data + go), (lds_void*)(B.stage + 16 + 1024 * m), 16, 0, MTBLX_NT_LOADS ? MTBLX_DMA_AUX : 0);
+        MTBLX_CHK(a.data + go, 16), MTBLX_LCHK(B.stage + 16 + 1024 * m, 1024), __builtin_amdgcn_global_load_lds((g_void*)(a.data + go), (lds_void*)(B.stage + 16 + 1024 * m), 16, 0, MTBLX_DMA_AUX);
       else if (c < nch)
         *reinterpret_cast<uint4*>(B.stage + 16 + 16 * c) = load_chunk(a, go);
     }
@@ -1606,7 +1506,7 @@ __device__ __forceinline__ void pipe_dma(PipeBuf<P>& B, const TileArgs& a, uint3
           if (c < nch) {
             if (go + 16 <= a.data_len && ((base + go) & 15ull) == 0)
               MTBLX_CHK(a.data + go, 16), MTBLX_LCHK(B.stage + so + 1024 * m, 1024), __builtin_amdgcn_global_load_lds((g_void*)(a.data + go), (lds_void*)(B.stage + so + 1024 * m), 16, 0,
-                                               MTBLX_NT_LOADS ? MTBLX_DMA_AUX : 0);
+                                               MTBLX_DMA_AUX);
             else
               *reinterpret_cast<uint4*>(B.stage + so + 16 * c) = load_chunk(a, go);
           }
@@ -2097,7 +1997,7 @@ __device__ __forceinline__ void wait_flag(const TileArgs& a, const uint32_t* fla
 
 template <class P>
 __device__ __forceinline__ void pipe_copy(const PipeBuf<P>& B, const TileArgs& a, int cw, int lane, const uint32_t* ready,
-                                          uint32_t want, Stamps& ST, uint8_t* mk, uint32_t rows = P::ROWS) {
+                                          uint32_t want, Stamps& ST, uint8_t* mk) {
   const uint32_t nint = B.nint, nb = B.nb;
   uint32_t fb = (uint32_t)cw * (kWave / 16);
   if (fb < nint) {
@@ -2106,7 +2006,7 @@ __device__ __forceinline__ void pipe_copy(const PipeBuf<P>& B, const TileArgs& a
     wait_flag(a, ready, want);
     ST.hit(0);
     if (a.write) copy_emit(B, a, r, lane, mk);
-    for (fb += rows; fb < nint; fb += rows) {   // wave-uniform
+    for (fb += P::ROWS; fb < nint; fb += P::ROWS) {   // wave-uniform
       const CopyRow r2 = copy_prepare(B, fb, lane);
       if (a.write) copy_emit(B, a, r2, lane, mk);
     }
@@ -2153,14 +2053,6 @@ __device__ __forceinline__ uint32_t crc_word4(const PipeLds<P>& S, uint32_t c, u
   return S.crcT[3][c & 0xffu] ^ S.crcT[2][(c >> 8) & 0xffu] ^ S.crcT[1][(c >> 16) & 0xffu] ^ S.crcT[0][c >> 24];
 }
 
-// Always inlined: under register pressure the compiler outlined a call of the round-2 CRC
-// routine (PipeLargeV's look-back wave) and the out-of-line call is what faulted (DESIGN.md §4,
-// "the spill fault"); MTBLX_CRC_NOINLINE (diagnostic builds only) forces the call.
-#ifdef MTBLX_CRC_NOINLINE
-#define MTBLX_PIPE_CRC_INLINE __attribute__((noinline))
-#else
-#define MTBLX_PIPE_CRC_INLINE __forceinline__
-#endif
 // MTBLX_ABL_CRC (diagnostic ablation builds only; results are wrong by construction):
 // bit 0 skips the window loop, bit 1 the stored-checksum reads, bit 2 the whole CRC
 #ifndef MTBLX_ABL_CRC
@@ -2169,14 +2061,8 @@ __device__ __forceinline__ uint32_t crc_word4(const PipeLds<P>& S, uint32_t c, u
 #ifndef MTBLX_CRC_WIN
 #define MTBLX_CRC_WIN 72     // window bytes (36: 0.375 ms, 72: 0.340 on cfg2 -- LDS lookups, not chains, bound it)
 #endif
-#ifndef MTBLX_CRC_INFLIGHT
-#define MTBLX_CRC_INFLIGHT 1 // window rounds in flight per lane (2: 0.416 ms at 72 B windows)
-#endif
 #ifndef MTBLX_CRC_UNROLL
 #define MTBLX_CRC_UNROLL 9   // window steps unrolled
-#endif
-#ifndef MTBLX_CRC_EARLY
-#define MTBLX_CRC_EARLY 0    // 1: before the copy (the tile is staged; the copy waits on the look-back)
 #endif
 constexpr uint32_t kCrcWinB = MTBLX_CRC_WIN;
 constexpr uint32_t kCrcRounds = (65664u + 64u * kCrcWinB - 1u) / (64u * kCrcWinB);   // rounds of the largest block
@@ -2248,102 +2134,16 @@ __device__ __forceinline__ void pipe_crc_final(const PipeBuf<P>& B, const TileAr
   }
 }
 
-// The fused checksum on the matrix cores (MTBLX_FUSED_MFMA=1, the A/B variant; the default, 0, is
-// the VALU slicing path below, which measured faster -- DESIGN §0.4 item 6): the staged blocks' CRC-32C
-// by the method of k_crc32c_mfma (crc_mfma.h) read straight from the tile's LDS stage.  Work unit
-// = (block j, super-window sw: 8 steps of 1 KiB counted from the block's 16-byte aligned end in
-// the stage); copy wave cw takes units cw, cw + NC, ... of the tile after its copy.  Per step a
-// lane reads its aligned 16-byte chunk (ds_read_b128), masks the bytes before the block start
-// and folds the init into bytes 0..3 (head_chunk), masks the pad after the block end
-// (tail_chunk), then 8 fp4 + 2 f16 MFMAs (mfma_step); per unit the column parities, the column
-// and super-window shifts and the pad removal x^(-8t) (nibble tables), XORed into the block's
-// accumulator.  Round 4's VALU window loop (slicing-by-4, MTBLX_FUSED_MFMA=0) is the product.
-#ifndef MTBLX_FUSED_MFMA
-#define MTBLX_FUSED_MFMA 0
-#endif
-constexpr int kDecSup = (65664 + mtblx_crc::kMStep * mtblx_crc::kMSup - 1) / (mtblx_crc::kMStep * mtblx_crc::kMSup) + 1;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"   // read only by the A/B path
-static __constant__ mtblx_crc::MfmaTabs kDecMfma = mtblx_crc::MfmaTabs();
-static __constant__ mtblx_crc::SwTabs<kDecSup> kDecSw = mtblx_crc::SwTabs<kDecSup>();
-#pragma clang diagnostic pop
-
-template <class P>
-__device__ __forceinline__ void pipe_crc_mfma(const PipeBuf<P>& B, PipeLds<P>& S, uint32_t cw, int lane, uint32_t par) {
-  using namespace mtblx_crc;
-  constexpr uint32_t NC = (uint32_t)P::NCOPY;
-  const uint32_t nb = B.nb;
-  const int g = lane >> 4, n = lane & 15;
-  const int32_t kx16 = 16 * (60 - 4 * n + g);   // the lane's chunk of a step
-  uint32_t u = 0;   // running unit number over the tile's blocks
-  for (uint32_t j = 0; j < nb; ++j) {
-    const uint32_t L = B.blen[j], bo = B.boff[j];
-    if (bo >= kOutOfBounds || L < 4u) continue;   // pipe_crc_final: from HBM / byte-wise
-    const uint32_t t = (16u - ((bo + L) & 15u)) & 15u, Lp = L + t;
-    const uint32_t steps = (Lp + kMStep - 1) / kMStep, nsup = (steps + kMSup - 1) / kMSup;
-    // this wave's units of block j: sw with (u + sw) % NC == cw
-    uint32_t sw = (cw + NC - u % NC) % NC;
-    u += nsup;
-    for (; sw < nsup; sw += NC) {
-      v4f c2a = {0.f, 0.f, 0.f, 0.f}, c2b = c2a;
-#pragma unroll 1
-      for (int tt = kMSup - 1; tt >= 0; --tt) {   // from the super-window's start
-        const uint32_t s = sw * kMSup + (uint32_t)tt;
-        if (s < steps) {
-          const int32_t pos = (int32_t)Lp - (int32_t)(kMStep * (s + 1)) + kx16;   // block position, 16-aligned in LDS
-          v4u x = {0u, 0u, 0u, 0u};
-          if (pos > -16) {
-            MTBLX_LCHK(B.stage + (int32_t)bo + pos, 16);
-            const uint4 w = *reinterpret_cast<const uint4*>(B.stage + (int32_t)bo + pos);
-            x = v4u{w.x, w.y, w.z, w.w};
-            if (pos < 4) x = head_chunk(x, pos);
-          }
-          if (s == 0 && t != 0 && lane == 48) x = tail_chunk(x, t);   // lane (g 3, n 0): the step's last chunk
-          // the stage-1 operands are read per step (L1 / L2 hits): held in registers through the
-          // tile loop they pushed the fused-verify kernels past 128 VGPRs into scratch
-          const v4i* pa = reinterpret_cast<const v4i*>(&kDecMfma.a[0][0][0][0]) + lane;
-          const v4i a2lo = reinterpret_cast<const v4i*>(&kDecMfma.a2[tt][0][0][0])[lane];
-          const v4i a2hi = reinterpret_cast<const v4i*>(&kDecMfma.a2[tt][1][0][0])[lane];
-          mfma_step_ld(pa, x, a2lo, a2hi, c2a, c2b);
-        }
-      }
-      uint32_t c = kDecMfma.col[n][g][par_nib(c2a)] ^ kDecMfma.col[n][4 + g][par_nib(c2b)];
-      c = row_xor(c);
-      uint32_t C = (uint32_t)__builtin_amdgcn_readlane((int)c, 0) ^ (uint32_t)__builtin_amdgcn_readlane((int)c, 16) ^
-                   (uint32_t)__builtin_amdgcn_readlane((int)c, 32) ^ (uint32_t)__builtin_amdgcn_readlane((int)c, 48);
-      const uint32_t jl = (uint32_t)lane & 15u;
-      if (sw) {   // x^(8·8192·sw)
-        const uint32_t v = jl < 8u ? kDecSw.t[sw][jl][(C >> (4 * jl)) & 15u] : 0u;
-        C = (uint32_t)__builtin_amdgcn_readlane((int)row_xor(v), 0);
-      }
-      if (t) {    // x^(-8t): the pad removed (linear: per unit, before the XOR of the units)
-        const uint32_t v = jl < 8u ? kDecMfma.inv[t][jl][(C >> (4 * jl)) & 15u] : 0u;
-        C = (uint32_t)__builtin_amdgcn_readlane((int)row_xor(v), 0);
-      }
-      if (lane == 0) __hip_atomic_fetch_xor(&S.cacc[par][j], C, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-  }
-}
-
 // copy wave cw (of NC) after its copy of tile B: its share of the windows, then the count; the
 // last of the NC waves finalises the tile
+// Always inlined: under register pressure the compiler outlined a call of the round-2 CRC
+// routine (PipeLargeV's look-back wave) and the out-of-line call is what faulted (DESIGN.md §4,
+// "the spill fault").
 template <class P>
-__device__ MTBLX_PIPE_CRC_INLINE void pipe_crc_copy(const PipeBuf<P>& B, const TileArgs& a, PipeLds<P>& S, uint32_t cw,
-                                                    int lane, uint32_t par) {
+__device__ __forceinline__ void pipe_crc_copy(const PipeBuf<P>& B, const TileArgs& a, PipeLds<P>& S, uint32_t cw,
+                                              int lane, uint32_t par) {
   if constexpr ((MTBLX_ABL_CRC & 4) != 0) return;
-#ifdef MTBLX_CALL_PROBE   // diagnostic (the outlined-call fault): the callee's arguments
-  if (lane == 0 && cw == 0 && blockIdx.x < 2)
-    printf("probe wg %u par %u B %p a %p data %p len %lu blk_off %p nblk %u crc %p bad %p "
-           "framed %d nb %u b0 %u boff0 %u blen0 %u S %p crcT %p\n",
-           blockIdx.x, par, (const void*)&B, (const void*)&a, (const void*)a.data, (unsigned long)a.data_len,
-           (const void*)a.blk_off, a.nblk, (void*)a.crc, (void*)a.crc_bad, a.crc_framed, B.nb, B.b0, B.boff[0],
-           B.blen[0], (void*)&S, (void*)&S.crcT[0][0]);
-#if MTBLX_CALL_PROBE == 1
-  return;   // arguments only: the body (and the fault) skipped
-#endif
-#endif
   constexpr uint32_t NC = (uint32_t)P::NCOPY;
-  constexpr int kIn = MTBLX_CRC_INFLIGHT;
   const uint32_t nb = B.nb;
   // copy wave 0: the stored checksums (framed batches), loaded now, written to LDS at the end
   uint32_t stored = 0, framed = 0;
@@ -2362,61 +2162,22 @@ __device__ MTBLX_PIPE_CRC_INLINE void pipe_crc_copy(const PipeBuf<P>& B, const T
   const uint32_t* st32 = reinterpret_cast<const uint32_t*>(B.stage);
   const uint32_t g = nb >= NC ? 1u : NC / nb;           // waves per block
   const uint32_t jstep = nb >= NC ? NC : nb;            // (nb < NC: one block per wave, then done)
-  if constexpr ((MTBLX_ABL_CRC & 1) == 0 && MTBLX_FUSED_MFMA) pipe_crc_mfma(B, S, cw, lane, par);
-  if constexpr ((MTBLX_ABL_CRC & 1) == 0 && !MTBLX_FUSED_MFMA)
+  if constexpr ((MTBLX_ABL_CRC & 1) == 0)
   for (uint32_t j = nb >= NC ? cw : cw / g; j < nb; j += jstep) {
     const uint32_t s = nb >= NC ? 0u : cw % g;
     const uint32_t L = B.blen[j], bo = B.boff[j];
     if (bo >= kOutOfBounds || L < 4u) continue;         // finalisation: from HBM / byte-wise
     const uint32_t nwin = (L + kCrcWinB - 1) / kCrcWinB, nr = (nwin + 63u) / 64u;
     uint32_t acc = 0;
-    if constexpr (kIn == 1) {
-      for (uint32_t r = s; r < nr; r += g) {
-        const uint32_t k = (uint32_t)lane + 64u * r;
-        uint32_t c = 0;
-        if (k < nwin) {
-          const int32_t p0 = (int32_t)L - (int32_t)(kCrcWinB * (k + 1u));
-          c = lds_window_raw(S, st32, (int32_t)bo + p0, p0);
-        }
-        acc ^= r ? mtblx_crc::dmultmodp(S.shX[r], c) : c;
+    // one window round in flight per lane (two side by side: 0.416 ms against 0.340 at 72 B windows)
+    for (uint32_t r = s; r < nr; r += g) {
+      const uint32_t k = (uint32_t)lane + 64u * r;
+      uint32_t c = 0;
+      if (k < nwin) {
+        const int32_t p0 = (int32_t)L - (int32_t)(kCrcWinB * (k + 1u));
+        c = lds_window_raw(S, st32, (int32_t)bo + p0, p0);
       }
-    } else
-    for (uint32_t r0 = s; r0 < nr; r0 += g * kIn) {
-      // rounds r0, r0 + g, ... (kIn of them) side by side: independent chains
-      uint32_t c[kIn], d0[kIn];
-      int32_t Aw[kIn], p0[kIn];
-#pragma unroll
-      for (int i = 0; i < kIn; ++i) {
-        const uint32_t k = (uint32_t)lane + 64u * (r0 + (uint32_t)i * g);
-        const bool on = r0 + (uint32_t)i * g < nr && k < nwin;
-        p0[i] = on ? (int32_t)L - (int32_t)(kCrcWinB * (k + 1u)) : (1 << 20);   // off: never masked, dropped
-        Aw[i] = on ? (int32_t)bo + p0[i] : 0;
-        d0[i] = Aw[i] >= 0 ? st32[Aw[i] >> 2] : 0u;
-        c[i] = 0;
-      }
-#pragma unroll MTBLX_CRC_UNROLL
-      for (int m = 0; m < (int)kCrcWinB / 4; ++m) {
-#pragma unroll
-        for (int i = 0; i < kIn; ++i) {
-          const int32_t qa = (Aw[i] >> 2) + m + 1;
-          const uint32_t d1 = qa >= 0 ? st32[qa] : 0u;
-          uint32_t w = __builtin_amdgcn_alignbit(d1, d0[i], (uint32_t)(Aw[i] & 3) * 8u);
-          d0[i] = d1;
-          const int32_t pos = p0[i] + 4 * m;           // block position of the word's first byte
-          if (pos < 4) {
-            const uint32_t keep = pos <= -4 ? 0u : (pos < 0 ? 0xFFFFFFFFu << (8u * (uint32_t)(-pos)) : 0xFFFFFFFFu);
-            const uint32_t fold = pos < 0 ? keep : 0xFFFFFFFFu >> (8u * (uint32_t)pos);
-            w = (w & keep) ^ fold;
-          }
-          c[i] = crc_word4(S, c[i], w);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < kIn; ++i) {
-        const uint32_t r = r0 + (uint32_t)i * g;
-        if (r >= nr || p0[i] == (1 << 20)) continue;
-        acc ^= r ? mtblx_crc::dmultmodp(S.shX[r], c[i]) : c[i];
-      }
+      acc ^= r ? mtblx_crc::dmultmodp(S.shX[r], c) : c;
     }
     acc = mtblx_crc::dmultmodp(S.shK[lane], acc);
 #pragma unroll
@@ -2435,27 +2196,6 @@ __device__ MTBLX_PIPE_CRC_INLINE void pipe_crc_copy(const PipeBuf<P>& B, const T
   pipe_crc_final(B, a, S, lane, par);
 }
 
-#ifdef MTBLX_LARGE_SERIAL
-constexpr bool kLargeSerial = true;   // A/B: the round-2 two-buffer schedule for PipeLarge
-#else
-constexpr bool kLargeSerial = false;
-#endif
-// Two-buffer schedule (PipeLarge): 1 = late walk (the DMA of tile it+1 into the free buffer at
-// the start of iteration it, beside the prepare + copy of tile it; the walker walks tile it+1 once
-// it has landed); 0 = walk of tile it+1 beside the copy of tile it, DMA of tile it+2 after it.
-#ifndef MTBLX_LARGE_LATE
-#define MTBLX_LARGE_LATE 1
-#endif
-#ifndef MTBLX_PHASE_DELAY     // A/B: PipeLarge workgroups of one half start this many cycles late
-#define MTBLX_PHASE_DELAY 0
-#endif
-#ifndef MTBLX_PHASE_SEL       // ... the half: 0 = odd workgroups, 1 = (g >> 3) odd (half of each XCD)
-#define MTBLX_PHASE_SEL 0
-#endif
-#ifndef MTBLX_LATE_LOADCOPY   // late walk: the loaders copy rows of tile it after their DMA
-#define MTBLX_LATE_LOADCOPY 0
-#endif
-
 // MTBLX_SPILL (diagnostic build only, `make spill`): keep kSpillPad extra VGPRs live across the
 // whole pipeline kernel, which pushes it past its 128 VGPRs into scratch -- checks that a
 // spilling build is still correct (tests/test_spill_gpu.py)
@@ -2472,18 +2212,15 @@ __global__ void __launch_bounds__(kPipeThreads, 1) k_decode_pipe(TileArgs a) {
     for (int i = 0; i < kSpillPad; ++i) spill_pad[i] = a.blk_len[((uint32_t)threadIdx.x + 7u * i) % a.nblk];   // loads: not rematerialisable
   }
   __shared__ PipeLds<P> S;
-  // Two buffers, serial: tile it is walked, looked back and copied in iteration it while the
-  // loaders stage tile it+1 (PipeLargeV: its fused CRC reads the tile being copied).  Otherwise
-  // the three-stage schedule: walk it+1 | look-back + copy it | DMA it+2 -- with two buffers
-  // the DMA of tile it+2 goes into tile it's buffer once the copy waves have left it.
-  constexpr bool serial2 = P::NBUF == 2 && (P::VERIFY || kLargeSerial);
-  // Two buffers, three stages: the loaders have nothing to do until the copy waves leave tile
-  // it's buffer, so they copy too (as copy waves NCOPY ..): 56 rows per pass, so a 64 KiB block
-  // (~53 restart intervals) takes one pass instead of 48 + 5.
-  constexpr bool kLate = P::NBUF == 2 && !serial2 && MTBLX_LARGE_LATE;
-  constexpr bool kLoadCopy = P::NBUF == 2 && !serial2 && (!kLate || MTBLX_LATE_LOADCOPY);
-  constexpr uint32_t kCopyW = P::NCOPY + (kLoadCopy ? P::LOADW : 0);   // waves that copy a tile
-  constexpr uint32_t kRows = kCopyW * (kWave / 16);
+  // Three schedules, one per loop below:
+  //  - serial, two buffers (PipeLargeV): tile it is walked, looked back and copied in iteration it
+  //    while the loaders stage tile it+1 (its fused CRC reads the tile being copied);
+  //  - late walk, two buffers (PipeLarge, PipeLargeP): the DMA of tile it+1 goes into the free
+  //    buffer at the start of iteration it, beside the prepare + copy of tile it, and the walker
+  //    walks tile it+1 once it has landed;
+  //  - three buffers (PipeSmall, PipeSmallV, PipeSmallP): walk it+1 | look-back + copy it | DMA it+2.
+  constexpr bool kSerial = P::NBUF == 2 && P::VERIFY;
+  constexpr bool kLate = P::NBUF == 2 && !P::VERIFY;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const uint32_t g = blockIdx.x, G = gridDim.x;
   const uint32_t nloc = (a.ntiles > g) ? (a.ntiles - g + G - 1) / G : 0;  // tiles of this workgroup
@@ -2527,26 +2264,15 @@ __global__ void __launch_bounds__(kPipeThreads, 1) k_decode_pipe(TileArgs a) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   } else if (wv == 1) {
-    if (!serial2 && nloc > 0) pipe_lookback_issue(a, g, G, lbv, lane);
+    if (!kSerial && nloc > 0) pipe_lookback_issue(a, g, G, lbv, lane);
   }
   __syncthreads();
   TL(1);
-#if MTBLX_PHASE_DELAY > 0
-  // A/B (diagnostic builds): start half of the workgroups MTBLX_PHASE_DELAY shader cycles late so
-  // that the two halves' DMA + store phases (HBM-bound) do not coincide
-  if constexpr (P::NBUF == 2) {
-    const bool late_half = MTBLX_PHASE_SEL == 0 ? (g & 1u) != 0u : ((g >> 3) & 1u) != 0u;
-    if (late_half) {
-      const uint64_t t0 = __builtin_amdgcn_s_memtime();
-      while (__builtin_amdgcn_s_memtime() - t0 < (uint64_t)MTBLX_PHASE_DELAY) __builtin_amdgcn_s_sleep(8);
-    }
-  }
-#endif
   if (wv == 0) __builtin_amdgcn_s_setprio(2);  // the walk is a serial latency chain
   uint64_t ntl = 0;
   uint32_t wmode = 0;   // wave 0: which interval walk goes first (pipe_walk)
 
-  if constexpr (serial2) {
+  if constexpr (kSerial) {
     for (uint32_t it = 0; it < nloc; ++it) {
       PipeBuf<P>& C = S.buf[it & 1u];
       const uint32_t tc = g + it * G;
@@ -2582,9 +2308,8 @@ __global__ void __launch_bounds__(kPipeThreads, 1) k_decode_pipe(TileArgs a) {
         ST.hit(1);
       } else {
         wait_flag(a, &S.pub, it + 1);
-        if constexpr (P::VERIFY && MTBLX_CRC_EARLY) pipe_crc_copy(C, a, S, (uint32_t)(wv - P::COPY0), lane, it & 1u);
         pipe_copy(C, a, wv - P::COPY0, lane, &S.ready, it + 1, ST, S.cmk[wv]);
-        if constexpr (P::VERIFY && !MTBLX_CRC_EARLY) pipe_crc_copy(C, a, S, (uint32_t)(wv - P::COPY0), lane, it & 1u);
+        pipe_crc_copy(C, a, S, (uint32_t)(wv - P::COPY0), lane, it & 1u);
         ST.hit(7);
       }
       raw_barrier();
@@ -2594,10 +2319,10 @@ __global__ void __launch_bounds__(kPipeThreads, 1) k_decode_pipe(TileArgs a) {
       else ST.hit(1);
     }
   } else if constexpr (kLate) {
-    // iteration it: the loaders stage tile it+1 into the buffer tile it-1 left, then (optionally)
-    // copy rows of tile it; the walker walks tile it+1 once both loaders' DMA has landed; the
-    // look-back and copy waves finish tile it meanwhile.  The DMA (HBM reads) now overlaps the
-    // copy's prepare and stores instead of following them.
+    // iteration it: the loaders stage tile it+1 into the buffer tile it-1 left; the walker walks
+    // tile it+1 once both loaders' DMA has landed; the look-back and copy waves finish tile it
+    // meanwhile.  The DMA (HBM reads) overlaps the copy's prepare and stores instead of following
+    // them.
     for (int it = -1; it < (int)nloc; ++it) {
       const uint32_t k1 = (uint32_t)(it + 1);
       if (wv == 0) {
@@ -2617,12 +2342,6 @@ __global__ void __launch_bounds__(kPipeThreads, 1) k_decode_pipe(TileArgs a) {
           if (lane == 0) __hip_atomic_fetch_add(&S.staged, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         ST.hit(4);
-        if constexpr (kLoadCopy) {
-          if (it >= 0) {
-            pipe_copy(S.buf[(uint32_t)it & 1u], a, P::NCOPY + (int)part, lane, &S.ready, (uint32_t)it + 1, ST, S.cmk[wv], kRows);
-            if (lane == 0) __hip_atomic_fetch_add(&S.cdone, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          }
-        }
         ST.hit(6);
       } else if (it >= 0) {
         PipeBuf<P>& C = S.buf[(uint32_t)it & 1u];
@@ -2639,11 +2358,11 @@ __global__ void __launch_bounds__(kPipeThreads, 1) k_decode_pipe(TileArgs a) {
               if (wb.expired(handoff_ticks(a))) { ws_timeout(a); break; }
             }
             pipe_lookback_issue(a, tc + G, G, lbv, lane);
-            pipe_lookback_poll(a, tc + G, G, lbv, lane, &S.cdone, (uint32_t)(it + 1) * kCopyW);
+            pipe_lookback_poll(a, tc + G, G, lbv, lane, &S.cdone, (uint32_t)(it + 1) * P::NCOPY);
           }
           ST.hit(1);
         } else {
-          pipe_copy(C, a, wv - P::COPY0, lane, &S.ready, (uint32_t)it + 1, ST, S.cmk[wv], kRows);
+          pipe_copy(C, a, wv - P::COPY0, lane, &S.ready, (uint32_t)it + 1, ST, S.cmk[wv]);
           if (wv == P::COPY0 && it + 1 == (int)nloc) TLW(9);
           if (wv == P::COPY0 + P::NCOPY - 1 && it + 1 == (int)nloc) TLW(10);
           if (lane == 0) __hip_atomic_fetch_add(&S.cdone, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2670,17 +2389,7 @@ __global__ void __launch_bounds__(kPipeThreads, 1) k_decode_pipe(TileArgs a) {
       }
       ST.hit(3);
     } else if (loader) {
-      if constexpr (kLoadCopy) {
-        if (it >= 0) {
-          pipe_copy(S.buf[(uint32_t)it % P::NBUF], a, P::NCOPY + (int)part, lane, &S.ready, (uint32_t)it + 1, ST, S.cmk[wv], kRows);
-          if (lane == 0) __hip_atomic_fetch_add(&S.cdone, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      }
       if (k2 < nloc) {
-        if constexpr (P::NBUF == 2) {
-          // tile it+2 goes into tile it's buffer: wait until every copy wave has left it
-          if (it >= 0) wait_flag(a, &S.cdone, (uint32_t)(it + 1) * kCopyW);
-        }
         pipe_dma(S.buf[k2 % P::NBUF], a, g + k2 * G, ioff, ilen, lane, part);
         load_info(k2 + 1);
       }
@@ -2704,16 +2413,15 @@ __global__ void __launch_bounds__(kPipeThreads, 1) k_decode_pipe(TileArgs a) {
             if (wb.expired(handoff_ticks(a))) { ws_timeout(a); break; }
           }
           pipe_lookback_issue(a, tc + G, G, lbv, lane);
-          pipe_lookback_poll(a, tc + G, G, lbv, lane, &S.cdone, (uint32_t)(it + 1) * kCopyW);
+          pipe_lookback_poll(a, tc + G, G, lbv, lane, &S.cdone, (uint32_t)(it + 1) * P::NCOPY);
         }
         ST.hit(1);
       } else {
-        if constexpr (P::VERIFY && MTBLX_CRC_EARLY) pipe_crc_copy(C, a, S, (uint32_t)(wv - P::COPY0), lane, (uint32_t)it & 1u);
-        pipe_copy(C, a, wv - P::COPY0, lane, &S.ready, (uint32_t)it + 1, ST, S.cmk[wv], kRows);
+        pipe_copy(C, a, wv - P::COPY0, lane, &S.ready, (uint32_t)it + 1, ST, S.cmk[wv]);
         if (wv == P::COPY0 && it + 1 == (int)nloc) TLW(9);   // first copy wave: last tile's stores issued
         if (wv == P::COPY0 + P::NCOPY - 1 && it + 1 == (int)nloc) TLW(10);
         if (lane == 0) __hip_atomic_fetch_add(&S.cdone, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if constexpr (P::VERIFY && !MTBLX_CRC_EARLY) pipe_crc_copy(C, a, S, (uint32_t)(wv - P::COPY0), lane, (uint32_t)it & 1u);
+        if constexpr (P::VERIFY) pipe_crc_copy(C, a, S, (uint32_t)(wv - P::COPY0), lane, (uint32_t)it & 1u);
         ST.hit(7);
       }
     }
@@ -2770,8 +2478,7 @@ __global__ void __launch_bounds__(kPipeThreads, 1) k_decode_pipe(TileArgs a) {
 #endif
 }
 
-using CfgSmall = TileCfg<32768, 640, 256, 64, true, 3>;
-using CfgLarge = TileCfg<67584, 1024, 256, 16, false, 1>;
+using CfgLarge = TileCfg<67584, 1024, 256, 16, 1>;
 struct CfgLargeP : CfgLarge { static constexpr bool VALPOS = true; };   // positions twin (see PipeSmallP)
 
 }  // namespace mtblx
@@ -2808,17 +2515,15 @@ Plan make_plan(uint32_t nblk, uint32_t max_len, bool verify) {
   } else if (fit_plan(max_len, verify ? PipeLargeV::TB : PipeLarge::TB, PipeLarge::MAXBLK, p)) {
     p.kind = 1;
   } else {
-    const uint32_t usable = CfgLarge::TB - 48;
-    const uint32_t slot = ((max_len + 30u) / 16u) * 16u, per = max_len + 16u;
     p.kind = 2;
-    p.slot = (max_len != 0 && slot <= usable) ? slot : usable;
-    p.bpt = std::max<uint32_t>(1, std::min<uint32_t>(usable / std::max(per, p.slot), CfgLarge::MAXBLK));
+    if (!fit_plan(max_len, CfgLarge::TB, CfgLarge::MAXBLK, p)) {   // empty, or larger than a slot: one block per tile
+      p.slot = CfgLarge::TB - 48;
+      p.bpt = 1;
+    }
   }
   p.ntiles = (nblk + p.bpt - 1) / p.bpt;
   return p;
 }
-
-
 
 // One workgroup per CU: every workgroup of a launch is resident, which the look-back between
 // workgroups needs.  MTBLX_PIPE_CUS caps it (diagnostic: several processes sharing one GPU, e.g.

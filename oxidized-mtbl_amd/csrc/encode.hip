@@ -220,20 +220,8 @@ static __constant__ X8Tab kX8 = X8Tab();
 // The block CRC on the matrix cores (crc_mfma.h): the operands of k_crc32c_mfma, plus the shift of
 // super-window S (8 KiB steps counted from the block's aligned end) x^(8·8192·S) as nibble tables,
 // S <= 8 for blocks assembled in LDS (kLdsBlock bytes)
-#ifndef MTBLX_ENC_CRC_MFMA
-#define MTBLX_ENC_CRC_MFMA 1
-#endif
 #if defined(MTBLX_ENC_ABL) && !defined(MTBLX_DIAG)
 #error "MTBLX_ENC_ABL is a timing ablation (wrong output): build it through a diagnostic target"
-#endif
-#ifndef MTBLX_ENC_CONTIG   // each thread owns contiguous entries (phase B without per-round scans)
-#define MTBLX_ENC_CONTIG 1
-#endif
-#ifndef MTBLX_ENC_LAZY_T   // slicing-by-4 tables built only by blocks that use them
-#define MTBLX_ENC_LAZY_T 1
-#endif
-#ifndef MTBLX_ENC_TW   // planned mode: stores before the block CRC, stage-2 operand per wave (see k_encode)
-#define MTBLX_ENC_TW 1
 #endif
 #ifndef MTBLX_ENC_CRC_UNROLL
 #define MTBLX_ENC_CRC_UNROLL 4
@@ -302,19 +290,8 @@ __device__ __forceinline__ uint64_t wg_excl_scan(EncLds& S, uint64_t x, uint64_t
   return before + inc - x;
 }
 
-#ifndef MTBLX_ENC_CARRY   // the next entry's offsets carried from this one (A/B: 0 = reload both ends)
-#define MTBLX_ENC_CARRY 1
-#endif
-#ifndef MTBLX_ENC_TAILV   // tails of 1..15 bytes as 8/4/2/1-byte pieces (0: byte stores, the A/B base)
-#define MTBLX_ENC_TAILV 1
-#endif
-#ifndef MTBLX_ENC_NT_STORES
-#define MTBLX_ENC_NT_STORES 1
-#endif
-
 // the last t (1..15) bytes of the 16-byte window w, stored at d
 __device__ __forceinline__ void store_tail(uint8_t* d, const v4u& w, uint32_t t) {
-#if MTBLX_ENC_TAILV
   // the window shifted right by r = 16 - t bytes (funnel shifts), then stored as pieces of 8,
   // 4, 2 and 1 bytes (the bits of t) instead of t byte stores: a wave paid for its longest tail
   const uint32_t r = 16u - t, dq = r >> 2, bs = r & 3u;
@@ -344,13 +321,6 @@ __device__ __forceinline__ void store_tail(uint8_t* d, const v4u& w, uint32_t t)
     off += 2;
   }
   if (t & 1u) d[off] = (uint8_t)(word(off >> 2) >> (8 * (off & 3u)));
-#else
-  for (uint32_t k = 0; k < t; ++k) {
-    const uint32_t q = 16 - t + k;
-    const uint32_t v = q < 4 ? w.x : q < 8 ? w.y : q < 12 ? w.z : w.w;
-    d[k] = (uint8_t)(v >> (8 * (q & 3)));
-  }
-#endif
 }
 
 // copy n bytes from global src to dst (LDS or global, generic pointer).  Four 16-byte loads
@@ -381,94 +351,11 @@ __device__ __forceinline__ void copy_bytes(uint8_t* dst, const uint8_t* src, uin
   }
 }
 
-// n bytes from src to dst as 16-byte chunks at offsets min(16 c, n - 16): the last, partial chunk
-// is the 16-byte window ending at n, rewriting bytes of the chunk before it with the same values,
-// so a field of n >= 16 bytes takes ceil(n / 16) whole loads and stores, issued four at a time --
-// one round trip for up to 64 bytes, no tail pieces.  A field of 1..15 bytes is the window ending
-// at n shifted down; with `fwd` (this thread rewrites the bytes after the field later: the key
-// suffix before its value) it goes out as one 16-byte store, else as 8/4/2/1-byte pieces.
-#ifndef MTBLX_ENC_OVER
-#define MTBLX_ENC_OVER 0
-#endif
-__device__ __forceinline__ void copy_over(uint8_t* dst, const uint8_t* src, uint32_t n, const uint8_t* base, bool fwd) {
-  if (n >= 16u) {
-    const uint32_t m = (n + 15u) >> 4;
-    for (uint32_t c = 0; c < m; c += 4) {
-      v4u w[4];
-#pragma unroll
-      for (uint32_t u = 0; u < 4; ++u) {
-        const uint32_t o = 16u * (c + u) < n - 16u ? 16u * (c + u) : n - 16u;
-        if (c + u < m) w[u] = *reinterpret_cast<const v4u*>(src + o);
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < 4; ++u) {
-        const uint32_t o = 16u * (c + u) < n - 16u ? 16u * (c + u) : n - 16u;
-        if (c + u < m) *reinterpret_cast<v4u*>(dst + o) = w[u];
-      }
-    }
-    return;
-  }
-  if (n == 0u) return;
-  if (src + n >= base + 16) {
-    const v4u w = *reinterpret_cast<const v4u*>(src + n - 16);
-    if (fwd) {   // bytes n..15 of the store are rewritten by this thread afterwards
-      const uint32_t r = 16u - n, dq = r >> 2, bs = r & 3u;
-      const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
-      uint32_t o[4];
-#pragma unroll
-      for (uint32_t i = 0; i < 4; ++i) {
-        const uint32_t lo = dq + i < 4 ? (dq + i == 0 ? ws[0] : dq + i == 1 ? ws[1] : dq + i == 2 ? ws[2] : ws[3]) : 0u;
-        const uint32_t hi = dq + i + 1 < 4 ? (dq + i + 1 == 1 ? ws[1] : dq + i + 1 == 2 ? ws[2] : ws[3]) : 0u;
-        o[i] = __builtin_amdgcn_alignbyte(hi, lo, bs);
-      }
-      *reinterpret_cast<v4u*>(dst) = v4u{o[0], o[1], o[2], o[3]};
-    } else {
-      store_tail(dst, w, n);
-    }
-  } else {
-    for (uint32_t k = 0; k < n; ++k) dst[k] = src[k];
-  }
-}
-
-// an entry's key suffix (kn bytes at ks) and value (vn bytes at vs), back to back at dst: when
-// both are at most 64 bytes (cfg3's common case) every load of both -- whole chunks and the two
-// tail windows -- is issued before the first store, one memory round trip instead of the 2-4 of
-// two copy_bytes calls (each waits for its chunks, then for its tail window)
-#ifndef MTBLX_ENC_EARLY   // planned mode: first entry's fields loaded beside phase A's sums
-#define MTBLX_ENC_EARLY 0
-#endif
-#ifndef MTBLX_ENC_KV
-#define MTBLX_ENC_KV 0
-#endif
+// an entry's key suffix (kn bytes at ks) and value (vn bytes at vs), back to back at dst
 __device__ __forceinline__ void copy_kv(uint8_t* dst, const uint8_t* ks, uint64_t kn, const uint8_t* kbase,
                                         const uint8_t* vs, uint64_t vn, const uint8_t* vbase) {
-  if (!MTBLX_ENC_KV || kn > 64 || vn > 64) {
-    copy_bytes(dst, ks, kn, kbase);
-    copy_bytes(dst + kn, vs, vn, vbase);
-    return;
-  }
-  const uint32_t nk = (uint32_t)kn / 16u, tk = (uint32_t)kn % 16u, nv = (uint32_t)vn / 16u, tv = (uint32_t)vn % 16u;
-  const bool wk = tk && ks + kn >= kbase + 16, wv = tv && vs + vn >= vbase + 16;
-  v4u K[4], V[4], KT = {0u, 0u, 0u, 0u}, VT = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (uint32_t u = 0; u < 4; ++u)
-    if (u < nk) K[u] = *reinterpret_cast<const v4u*>(ks + 16 * u);
-  if (wk) KT = *reinterpret_cast<const v4u*>(ks + kn - 16);
-#pragma unroll
-  for (uint32_t u = 0; u < 4; ++u)
-    if (u < nv) V[u] = *reinterpret_cast<const v4u*>(vs + 16 * u);
-  if (wv) VT = *reinterpret_cast<const v4u*>(vs + vn - 16);
-#pragma unroll
-  for (uint32_t u = 0; u < 4; ++u)
-    if (u < nk) *reinterpret_cast<v4u*>(dst + 16 * u) = K[u];
-  if (wk) store_tail(dst + 16 * nk, KT, tk);
-  else for (uint32_t k = 16 * nk; k < (uint32_t)kn; ++k) dst[k] = ks[k];
-  uint8_t* dv = dst + kn;
-#pragma unroll
-  for (uint32_t u = 0; u < 4; ++u)
-    if (u < nv) *reinterpret_cast<v4u*>(dv + 16 * u) = V[u];
-  if (wv) store_tail(dv + 16 * nv, VT, tv);
-  else for (uint32_t k = 16 * nv; k < (uint32_t)vn; ++k) dv[k] = vs[k];
+  copy_bytes(dst, ks, kn, kbase);
+  copy_bytes(dst + kn, vs, vn, vbase);
 }
 
 __device__ __forceinline__ void put32(uint8_t* p, uint32_t v) {
@@ -682,14 +569,11 @@ __device__ __forceinline__ uint64_t vbytes32(uint32_t v, uint32_t len) {
                      ((uint64_t)(v & 0xfe00000u) << 3) | ((uint64_t)(v >> 28) << 32);
   return g | (0x0000008080808080ull & ((1ull << (8 * (len - 1u))) - 1ull));
 }
-#ifndef MTBLX_ENC_HDR   // the three header varints as one 8-byte store when they fit (1) or byte by byte (0)
-#define MTBLX_ENC_HDR 1
-#endif
 __device__ __forceinline__ void put_entry(uint8_t* dst, const Recs& R, const Ent& e) {
   const uint32_t sh = (uint32_t)e.sh, ks = (uint32_t)(e.kl - e.sh), vl = (uint32_t)e.vl;   // < 4 GiB (k_plan)
   const uint32_t l0 = vlen32(sh), l1 = vlen32(ks), l2 = vlen32(vl);
   const uint32_t n = l0 + l1 + l2;
-  if (MTBLX_ENC_HDR && n <= 8u && (uint64_t)n + ks + vl >= 8u) {
+  if (n <= 8u && (uint64_t)n + ks + vl >= 8u) {
     // one unaligned 8-byte store: its bytes n..7 are the key suffix / value's, rewritten below by
     // this thread (in program order) -- no conditional byte stores
     *reinterpret_cast<u64u*>(dst) = vbytes32(sh, l0) | (vbytes32(ks, l1) << (8 * l0)) | (vbytes32(vl, l2) << (8 * (l0 + l1)));
@@ -698,12 +582,7 @@ __device__ __forceinline__ void put_entry(uint8_t* dst, const Recs& R, const Ent
     put_varint(dst + l0, ks, l1);
     put_varint(dst + l0 + l1, vl, l2);
   }
-#if MTBLX_ENC_OVER
-  copy_over(dst + n, R.keys + e.k0 + e.sh, ks, R.keys, (uint64_t)ks + vl >= 16u);
-  copy_over(dst + n + ks, R.vals + e.v0, vl, R.vals, false);
-#else
   copy_kv(dst + n, R.keys + e.k0 + e.sh, e.kl - e.sh, R.keys, R.vals + e.v0, e.vl, R.vals);
-#endif
 }
 __device__ __forceinline__ uint64_t lookback(const EncArgs& a, uint32_t b, int lane, bool& timeout) {
   uint64_t excl = 0;
@@ -745,17 +624,6 @@ __device__ __forceinline__ uint64_t lookback(const EncArgs& a, uint32_t b, int l
 #define ESTAMP(k) do { } while (0)
 #endif
 
-#ifndef MTBLX_ENC_RAWB   // TW path: LDS-only barriers (1) or __syncthreads (0: also waits for the block's stores)
-#define MTBLX_ENC_RAWB 0
-#endif
-__device__ __forceinline__ void tw_barrier() {
-#if MTBLX_ENC_RAWB
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
-  __syncthreads();
-#endif
-}
-
 template <bool PL>   // PL: planned mode (sizes and offsets from the block cut's sums; no look-back)
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(MTBLX_ENC_WPE))) k_encode(EncArgs a) {   // 2 per CU
   __shared__ EncLds S;
@@ -776,9 +644,6 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
       }
     }
   };
-#if !MTBLX_ENC_LAZY_T
-  build_tables();
-#endif
   uint32_t b = blockIdx.x;
   if constexpr (!PL) {   // ticket order: every earlier block is running or done (the look-back)
     if (tid == 0) S.sh_u32[0] = atomicAdd(a.ticket, 1u);
@@ -786,7 +651,6 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
     b = S.sh_u32[0];
   }
   if (b >= a.nblk) return;
-#if MTBLX_ENC_TW
   // planned mode: the file offset and the Horner table of the block CRC (below) loaded now, so
   // their latency overlaps the assembly
   uint64_t tw_fin = 0;
@@ -798,7 +662,6 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
     }
     if (tid < 128) tw_swk = (&kEncMfma.swk[0][0])[tid];
   }
-#endif
   const uint64_t r0 = a.blk_rec[b], n = a.blk_rec[b + 1] - r0;
   const uint32_t iv = a.interval;
   ESTAMP(2);   // tables + ticket
@@ -808,7 +671,6 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
   // planned mode: the block's record range must lie in the plan
   const bool pl_ok = !PL || (r0 >= a.plo && r0 + n <= a.plo + a.pm);
   const uint64_t j0 = PL ? r0 - a.plo : 0;
-#if MTBLX_ENC_CONTIG
   // thread t owns the contiguous entries [i0, i1) (balanced: floor(n / threads) or one more
   // each): the scan of its byte total is the offset of its first entry, so phase B runs through
   // them with a running offset -- no per-round scans (two barriers each) and no round-wide wait
@@ -818,30 +680,12 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
   // the restart phase of entry i0 (i0 mod interval), then advanced per entry
   const uint32_t ph0 = iv ? (uint32_t)(i0 % iv) : 0u;
   uint32_t ph = ph0;
-  // planned mode: the first entry's fields are loaded now, beside the sums' loads (phase A), not
-  // after them
-  Ent en0{};
-  (void)en0;
-  if constexpr (PL && MTBLX_ENC_EARLY) {
-    if (pl_ok && i0 < i1) en0 = entry_of(a.R, r0, i0, iv ? (i0 > 0 && ph0 != 0) : (i0 > 0), nullptr, a.SH + j0);
-  }
-  Ent pe{};   // the previous entry (MTBLX_ENC_CARRY)
-  (void)pe;
+  Ent pe{};   // the previous entry: the next one's offsets are carried from it, not reloaded
   for (uint64_t i = i0; i < i1 && !PL; ++i) {
     const bool share = iv ? (i > 0 && ph != 0) : (i > 0);
     if (iv && ++ph == iv) ph = 0;
-#if MTBLX_ENC_CARRY
     const Ent e = i == i0 ? entry_of(a.R, r0, i, share) : entry_after(a.R, r0, i, pe, share);
     pe = e;
-#else
-    const Ent e = entry_of(a.R, r0, i, share);
-#endif
-#else
-  static_assert(!PL, "planned mode needs MTBLX_ENC_CONTIG");
-  for (uint64_t i = tid; i < n; i += kThreads) {
-    const bool share = shares(i, iv);
-    const Ent e = entry_of(a.R, r0, i, share);
-#endif
     part += entry_bytes(e.sh, e.kl, e.vl);
     if (i < kShCache)
       S.shc[i] = e.sh < 0xFFFFu ? (uint16_t)e.sh : (uint16_t)0xFFFFu;
@@ -850,14 +694,11 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
   if constexpr (PL) {   // the sums give every offset: no size pass, no scan
     if (pl_ok) {
       entries = planned_off(a, j0, n, iv);
-#if MTBLX_ENC_CONTIG
       tbase = planned_off(a, j0, i0, iv);
-#endif
     }
   } else {
     tbase = wg_excl_scan(S, part, entries);
   }
-  (void)tbase;
   // restarts: [0] + one push per restart entry (src/block_builder.rs:21, :60)
   const uint64_t nrest = n == 0 ? 1 : (iv == 0 ? 2 : 1 + (n - 1) / iv);
   int32_t st = MTBLX_ST_OK;
@@ -877,7 +718,6 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
   const uint64_t R = entries;   // restart array offset
   auto assemble = [&](uint8_t* dst, auto lds_tag) {
     constexpr bool lds = decltype(lds_tag)::value;
-#if MTBLX_ENC_CONTIG
     uint64_t eo = tbase;
     Ent en{};   // the next entry's fields are loaded before this entry's bytes move
     const uint32_t* SHb = PL ? a.SH + j0 : nullptr;
@@ -885,52 +725,24 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
     uint32_t rp = ph0;
     uint64_t ri = iv ? (i0 + iv - 1) / iv : 0;
     const auto share_at = [&](uint64_t i, uint32_t p) { return iv ? (i > 0 && p != 0) : (i > 0); };
-    if (i0 < i1) en = (PL && MTBLX_ENC_EARLY) ? en0 : entry_of(a.R, r0, i0, share_at(i0, rp), S.shc, SHb);
+    if (i0 < i1) en = entry_of(a.R, r0, i0, share_at(i0, rp), S.shc, SHb);
     for (uint64_t i = i0; i < i1; ++i) {
       const Ent e = en;
       const uint32_t rp1 = iv ? (rp + 1 == iv ? 0u : rp + 1) : 0u;
-#if MTBLX_ENC_CARRY
       if (i + 1 < i1) en = entry_after(a.R, r0, i + 1, e, share_at(i + 1, rp1), S.shc, SHb);
-#else
-      if (i + 1 < i1) en = entry_of(a.R, r0, i + 1, share_at(i + 1, rp1), S.shc, SHb);
-#endif
       const uint64_t sz = entry_bytes(e.sh, e.kl, e.vl);
-      {
-#else
-    uint64_t carry = 0;
-    for (uint64_t base = 0; base < n; base += kThreads) {
-      const uint64_t i = base + tid;
-      Ent e{};
-      uint64_t sz = 0;
-      if (i < n) {
-        e = entry_of(a.R, r0, i, shares(i, iv), S.shc);
-        sz = entry_bytes(e.sh, e.kl, e.vl);
-      }
-      uint64_t tot = 0;
-      const uint64_t eo = carry + wg_excl_scan(S, sz, tot);
-      if (i < n) {
-#endif
 #if defined(MTBLX_ENC_ABL) && MTBLX_ENC_ABL == 1   // timing ablation only (wrong output): no global loads in the copy
-        {
-          const uint32_t l0 = vlen32(e.sh), l1 = vlen32(e.kl - e.sh), l2 = vlen32(e.vl);
-          copy_bytes(dst + eo + l0 + l1 + l2, dst + eo, e.kl - e.sh + e.vl, dst);
-        }
+      {
+        const uint32_t l0 = vlen32(e.sh), l1 = vlen32(e.kl - e.sh), l2 = vlen32(e.vl);
+        copy_bytes(dst + eo + l0 + l1 + l2, dst + eo, e.kl - e.sh + e.vl, dst);
+      }
 #elif defined(MTBLX_ENC_ABL) && MTBLX_ENC_ABL == 2   // timing ablation only: no entry bytes at all
 #else
-        put_entry(dst + eo, a.R, e);
+      put_entry(dst + eo, a.R, e);
 #endif
-#if MTBLX_ENC_CONTIG
-        if (iv > 0 && rp == 0) put32(dst + R + 4 * ri++, (uint32_t)eo);
-        rp = rp1;
-#else
-        if (iv > 0 && i % iv == 0) put32(dst + R + 4 * (i / iv), (uint32_t)eo);
-#endif
-      }
-#if MTBLX_ENC_CONTIG
+      if (iv > 0 && rp == 0) put32(dst + R + 4 * ri++, (uint32_t)eo);
+      rp = rp1;
       eo += sz;
-#else
-      carry += tot;
-#endif
     }
     if (tid == 0) {
       if (n == 0 || iv == 0) put32(dst + R, 0u);      // restarts[0] = 0 (entry 0 writes it otherwise)
@@ -943,7 +755,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
   if (in_lds) assemble(S.ob, std::true_type{});
   ESTAMP(4);   // assembly in LDS
 
-#if MTBLX_ENC_TW && !defined(MTBLX_ENC_ABL)
+#ifndef MTBLX_ENC_ABL
   // Planned mode with the block CRC on the matrix cores (cfg3's path).  The file offset is known
   // (the scan of the framed sizes), so the block streams out right after the assembly and the
   // CRC runs beside its stores; only the 4-byte checksum of the frame waits for it.  The CRC's
@@ -955,7 +767,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
   // x^(8·8192) (a 512-byte nibble table in LDS) and the waves' partial column words XOR-combined.
   if constexpr (PL) {
     static_assert(kWaves == mtblx_crc::kMSup, "one wave per step position of a super-window");
-    if (MTBLX_ENC_CRC_MFMA && a.framed && in_lds && L >= 256 && st == MTBLX_ST_OK) {   // uniform
+    if (a.framed && in_lds && L >= 256 && st == MTBLX_ST_OK) {   // uniform
       using namespace mtblx_crc;
       const int g = lane >> 4, nn = lane & 15;
       v4i A[kMKs][2];
@@ -969,7 +781,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
       uint32_t(*hk)[16] = reinterpret_cast<uint32_t(*)[16]>(&S.T[0][0]);   // x^(8·8192): swk
       if (tid < 128) (&hk[0][0])[tid] = tw_swk;
       if (tid == 0) S.sh_u64[0] = tw_fin - F;
-      tw_barrier();   // the block (and its zero pad), the table, the offset
+      __syncthreads();   // the block (and its zero pad), the table, the offset
 #pragma unroll
       for (int k = 0; k < kMKs; ++k) asm volatile("" ::"v"(A[k][0]), "v"(A[k][1]));
       asm volatile("" ::"v"(a2lo), "v"(a2hi));   // the operands' wait is here, before the stores
@@ -981,11 +793,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
         const uint64_t nch = L / 16;
         for (uint64_t c = tid; c < nch; c += kThreads) {
           const v4a x = *reinterpret_cast<const v4a*>(S.ob + 16 * c);
-#if MTBLX_ENC_NT_STORES
           __builtin_nontemporal_store(v4u{x.x, x.y, x.z, x.w}, reinterpret_cast<v4u*>(dst + 16 * c));
-#else
-          *reinterpret_cast<v4u*>(dst + 16 * c) = v4u{x.x, x.y, x.z, x.w};
-#endif
         }
         for (uint64_t o = 16 * nch + tid; o < L; o += kThreads) dst[o] = S.ob[o];
       }
@@ -1012,7 +820,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
       }
       uint32_t* part = reinterpret_cast<uint32_t*>(S.shc);   // planned mode never reads shc
       part[w * kWave + lane] = acc;
-      tw_barrier();   // the parts (LDS); the block's stores stay in flight
+      __syncthreads();   // the parts (LDS); also waits for this wave's stores of the block
       ESTAMP(6);   // stores issued + CRC
       if (w == 0 && fits) {   // column shift x^(8·64·n), XOR over the columns, pad removal x^(-8t)
         uint32_t pw = 0;
@@ -1057,7 +865,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
 #if defined(MTBLX_ENC_ABL) && MTBLX_ENC_ABL == 3   // timing ablation only (wrong checksums): no block CRC
   const bool crc_mfma = false;
 #else
-  const bool crc_mfma = MTBLX_ENC_CRC_MFMA && a.framed && in_lds && L >= 4;
+  const bool crc_mfma = a.framed && in_lds && L >= 4;
 #endif
   if (crc_mfma) {
     __syncthreads();   // the assembled block (entries, restarts, count, pad) before its CRC
@@ -1090,7 +898,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
       src = dst;
     }
     if (a.framed) {
-#if MTBLX_ENC_LAZY_T && !(defined(MTBLX_ENC_ABL) && MTBLX_ENC_ABL == 3)
+#if !(defined(MTBLX_ENC_ABL) && MTBLX_ENC_ABL == 3)
       if (!crc_mfma) {   // uniform over the workgroup
         build_tables();
         __syncthreads();
@@ -1116,11 +924,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(M
       const uint64_t nch = L / 16;
       for (uint64_t c = tid; c < nch; c += kThreads) {
         const v4a x = *reinterpret_cast<const v4a*>(S.ob + 16 * c);
-#if MTBLX_ENC_NT_STORES   // the framed file bytes are written once: stream them out
+        // the framed file bytes are written once: stream them out
         __builtin_nontemporal_store(v4u{x.x, x.y, x.z, x.w}, reinterpret_cast<v4u*>(dst + 16 * c));
-#else
-        *reinterpret_cast<v4u*>(dst + 16 * c) = v4u{x.x, x.y, x.z, x.w};
-#endif
       }
       for (uint64_t o = 16 * nch + tid; o < L; o += kThreads) dst[o] = S.ob[o];
     }

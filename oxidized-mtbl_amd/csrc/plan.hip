@@ -279,12 +279,11 @@ __device__ __forceinline__ uint64_t est(const NextArgs& a, uint64_t j, uint64_t 
   return buf + nr * (buf > 0xFFFFFFFFull ? 8u : 4u) + 4u;
 }
 
-#ifndef MTBLX_PLAN_BATCH   // the direct probes as one batch of four loads (1: 14.5-14.7 ms) or one by one (0: 14.8)
-#define MTBLX_PLAN_BATCH 1
-#endif
-#ifndef MTBLX_PLAN_LIN   // records probed one by one after ka before the 64-record chunk skip (0: 16.0 ms, 4: 14.9 ms per 3 cfg3 chunks)
+#ifndef MTBLX_PLAN_LIN   // records probed directly after ka before the 64-record chunk skip (0: 16.0 ms, 4: 14.9 ms per 3 cfg3 chunks)
 #define MTBLX_PLAN_LIN 4
 #endif
+constexpr uint32_t kLin = MTBLX_PLAN_LIN;
+static_assert(kLin >= 1, "find_next probes at least ka itself before it skips by chunks");
 // next(j) for a start j of a shard ending at e (j + 1 < e, interval >= 1).  The first k with
 // est(k) + gmax >= B (est grows with k) is bracketed by a gallop from `guess` (first step d) and
 // bisected -- ka, returned for the next start's guess; from there the flushing record is found
@@ -326,27 +325,20 @@ __device__ __forceinline__ uint64_t find_next(const NextArgs& a, uint64_t j, uin
   uint64_t k = hi;
   // the flushing record is usually within a few records of ka (gm bounds every record's term
   // from above): probe those directly before skipping by 64-record chunks
-#if MTBLX_PLAN_BATCH
-  {   // the four probes' loads issued together (one round trip), then tested in order
-    uint64_t ev[4], gv[4];
+  {   // the probes' loads issued together (one round trip: 14.5-14.7 ms against 14.8 one by one), then tested in order
+    uint64_t ev[kLin], gv[kLin];
 #pragma unroll
-    for (uint32_t u = 0; u < 4; ++u) {
+    for (uint32_t u = 0; u < kLin; ++u) {
       const uint64_t kc = k + u <= e1 ? k + u : k;   // k <= e1 here
       MTBLX_CHK(a.G + kc, 8);
       gv[u] = a.G[kc];
       ev[u] = est(a, j, base_a, base_q, kc);
     }
 #pragma unroll
-    for (uint32_t u = 0; u < 4; ++u)
+    for (uint32_t u = 0; u < kLin; ++u)
       if (k + u <= e1 && ev[u] + gv[u] >= a.B) return k + u;
-    k = k + 4 <= e1 + 1 ? k + 4 : e1 + 1;
+    k = k + kLin <= e1 + 1 ? k + kLin : e1 + 1;
   }
-#else
-  for (uint32_t t = 0; t < MTBLX_PLAN_LIN && k <= e1; ++t, ++k) {
-    MTBLX_CHK(a.G + k, 8);
-    if (est(a, j, base_a, base_q, k) + a.G[k] >= a.B) return k;
-  }
-#endif
   while (k <= e1) {
     const uint64_t cl = std::min<uint64_t>((k | 63u), e1);
     MTBLX_CHK(a.GM + (k >> 6), 8);

@@ -714,9 +714,6 @@ typedef uint32_t v4u __attribute__((ext_vector_type(4), aligned(1)));
 #ifndef MTBLX_LANE_THREADS   // decoding lanes per workgroup (as many writer lanes again); 128: 1.045-1.049 ms vs 1.073-1.074 at 256, 1.091 at 64 (round 6)
 #define MTBLX_LANE_THREADS 128
 #endif
-#ifndef MTBLX_LANE_RING_ALL5   // ring_put writes all five words (no per-word branch)
-#define MTBLX_LANE_RING_ALL5 1
-#endif
 #ifndef MTBLX_LANE_RING_WORDS   // per-lane ring, 4-byte words (a power of two)
 #define MTBLX_LANE_RING_WORDS 64
 #endif
@@ -789,20 +786,12 @@ __device__ __forceinline__ void ring_put(uint32_t (*R)[kThreads], int t, uint32_
   w[2] = r ? alignb(v.w[2], v.w[1], 4u - r) : v.w[2];
   w[3] = r ? alignb(v.w[3], v.w[2], 4u - r) : v.w[3];
   w[4] = r ? v.w[3] >> (32u - 8u * r) : 0u;
-  const uint32_t e = r + cnt, nw = (e + 3u) >> 2;
-#if MTBLX_LANE_RING_ALL5
-  // all five words, unconditionally: the words past the chunk hold bytes at or past the new
-  // position, which no reader uses before a later put rewrites them (the carry lives in a
-  // register), and room() has already waited for the writer to take up to position + 20
-  (void)nw;
+  // all five words, unconditionally (no per-word branch): the words past the chunk hold bytes at
+  // or past the new position, which no reader uses before a later put rewrites them (the carry
+  // lives in a register), and room() has already waited for the writer to take up to position + 20
 #pragma unroll
   for (int k = 0; k < 5; ++k) R[(q + k) & (kRingWords - 1)][t] = w[k];
-#else
-#pragma unroll
-  for (int k = 0; k < 5; ++k)
-    if ((uint32_t)k < nw) R[(q + k) & (kRingWords - 1)][t] = w[k];
-#endif
-  const uint32_t c = e >> 2;
+  const uint32_t c = (r + cnt) >> 2;
   carry = c == 0u ? w[0] : c == 1u ? w[1] : c == 2u ? w[2] : c == 3u ? w[3] : w[4];
 }
 // ring: output bytes [x, x + 16) (x >= d - 255; bytes at or past d are whatever the ring holds)
@@ -986,14 +975,10 @@ __global__ void __launch_bounds__(2 * kThreads) k_snappy_lanes(const uint8_t* sr
       }
     }
   };
-  // output bytes [x, x + 16) from HBM once the writer's stores cover [x, lim): device-coherent loads
-#ifndef MTBLX_LANE_FAR_CACHED
-#define MTBLX_LANE_FAR_CACHED 1
-#endif
+  // output bytes [x, x + 16) from HBM once the writer's stores cover [x, lim)
   // (Round 3: a far copy's next chunk -- and a long literal's from HBM -- loaded one iteration
   // ahead measured 346-348 GB/s against 354-355 (profiles/r03/late/snap_pf); not kept.)
   auto far16 = [&](uint32_t x) {
-#if MTBLX_LANE_FAR_CACHED
     // Wait until the writer's completed stores cover every 128-byte line the 16 bytes touch, then
     // read them with an ordinary (cacheable) load: a line this CU caches was complete when it
     // was loaded, so no copy of it can be stale.  (Lines shared with a neighbouring block's slot
@@ -1002,9 +987,6 @@ __global__ void __launch_bounds__(2 * kThreads) k_snappy_lanes(const uint8_t* sr
     // per dword in ~80 % of the wave's iterations.
     const uintptr_t base = reinterpret_cast<uintptr_t>(dg);
     const uint32_t lim = (uint32_t)((((base + x + 15u) | 127u) + 1u) - base);
-#else
-    const uint32_t lim = x + 16u;
-#endif
     uint64_t t0 = 0;
     uint32_t spins = 0;
     while (vld(&Y.fvis[t]) < lim && !hang) {
@@ -1020,17 +1002,7 @@ __global__ void __launch_bounds__(2 * kThreads) k_snappy_lanes(const uint8_t* sr
     // returned: it depends on the branch).  The 128-byte bound assumes L1 lines of at most 128
     // bytes (gfx950's vector L1 line is 128 bytes).
     __asm__ volatile("" ::: "memory");
-#if MTBLX_LANE_FAR_CACHED
     return q4(*reinterpret_cast<const v4u*>(dg + x));
-#else
-    const uint8_t* p = dg + x;
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(reinterpret_cast<uintptr_t>(p) & ~(uintptr_t)3);
-    const uint32_t r = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
-    uint32_t w[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) w[k] = __hip_atomic_load(a + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return Q4{{alignb(w[1], w[0], r), alignb(w[2], w[1], r), alignb(w[3], w[2], r), alignb(w[4], w[3], r)}};
-#endif
   };
   // The loop emits ONE chunk (up to 16 bytes) per iteration: the next chunk of the current
   // element, or -- once it is done -- the first chunk of the next one.  An element-per-iteration

@@ -29,12 +29,18 @@ def rows(pattern):
 
 
 # the product decode of the cfg2 batch: k_decode_pipe<PipeSmall> (not the fused-verify variant)
-KERNEL_MATCH = "PipeCfg<49152, 3, 16, 56, false"
+# matched on the part of its name that does not carry the staging size (49 152 before round 6,
+# 49 664 since), as scripts/summarize_evidence.py does
+KERNEL_MATCH = ", 3, 16, 56, false"
+
+
+def is_product(name):
+    return "k_decode_pipe" in name and KERNEL_MATCH in name
 
 
 def counter(d, name, kernel):
     vals = [float(r["Counter_Value"]) for r in rows(os.path.join(d, "**", "*counter_collection.csv"))
-            if r.get("Counter_Name") == name and KERNEL_MATCH in r.get("Kernel_Name", "")]
+            if r.get("Counter_Name") == name and is_product(r.get("Kernel_Name", ""))]
     # the full-batch launches (the bench's end-to-end section decodes smaller chunks)
     top = max(vals) if vals else 0.0
     return [v for v in vals if v >= 0.9 * top]
@@ -60,7 +66,7 @@ def main():
     write = counter(os.path.join(src, "write"), "WRITE_SIZE", kernel)
     for name, d in (("fetch", "FETCH_SIZE"), ("write", "WRITE_SIZE")):
         sel = [r for r in rows(os.path.join(src, name, "**", "*counter_collection.csv"))
-               if r.get("Counter_Name") == d and KERNEL_MATCH in r.get("Kernel_Name", "")]
+               if r.get("Counter_Name") == d and is_product(r.get("Kernel_Name", ""))]
         if sel:
             with open(os.path.join(dst, f"pmc_{name}.csv"), "w", newline="") as fh:
                 w = csv.DictWriter(fh, fieldnames=list(sel[0].keys()))

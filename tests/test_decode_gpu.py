@@ -341,6 +341,63 @@ def test_pipelarge_max_shapes(oracle):
             assert not bad.cpu().numpy().any()
 
 
+@pytest.mark.parametrize("max_len", [49089, 49090, 49601, 49602])
+def test_kernel_choice_edges(oracle, max_len):
+    """The block lengths at which make_plan changes kernel.  A block fits PipeSmall's 49 664
+    staging bytes up to 49 601 B and PipeSmallV's 49 152 up to 49 089 B (fit_plan: the length + 30
+    rounded down to 16 may not exceed the staging bytes - 48), so a batch whose largest block is
+    49 089 B runs PipeSmall / PipeSmallV, 49 090 and 49 601 B PipeSmall but PipeLargeV for the
+    fused verify, and 49 602 B PipeLarge / PipeLargeV (the positions twins alike).  Each batch:
+    two shapes of exactly that length (restart interval 16 with 700 records, interval 1 with 150),
+    two copies each, among 4 KiB cfg2 blocks at unaligned offsets; every decode surface against
+    the oracle."""
+    codec = _dev()
+    import torch
+    import valpos_util as vu
+    from mtblx import synth
+    rng = np.random.default_rng(max_len)
+    cd, co, cl = synth.cfg2_file(5)
+    small = [bytes(cd[int(o): int(o) + int(n)]) for o, n in zip(co, cl)]
+    a = _block_of_len(oracle, rng, max_len, 16, 700, 24)
+    b = _block_of_len(oracle, rng, max_len, 1, 150, 40)
+    blocks = [small[0], a, small[1], b, small[2], a, b, small[3], small[4]]
+    d, o, l = corpus.pack(blocks, lead=3)
+    assert int(l.max()) == max_len and len(a) == len(b) == max_len
+    orc = oracle.decode_blocks(d, o, l)
+    assert (orc.status == 0).all()
+    exp_crc = np.array([oracle.crc32c(x) for x in blocks], np.uint32)
+    nr = int(orc.nrec.sum())
+    batch = codec.DeviceBatch.from_host(d, o, l)
+    ws = codec.Workspace(batch.nblk)
+    # plain decode into outputs of the exact size
+    out = codec.DecodedBlocks(batch.nblk, nr, orc.keys.size, orc.vals.size)
+    codec.decode_into(batch, out, ws)
+    torch.cuda.synchronize()
+    assert_same(out.to_host(), orc, o.size)
+    # decode + checksums, one launch and two
+    for fused in (True, False):
+        out, crc, bad = codec.decode_verify(batch, framed=False, fused=fused)
+        torch.cuda.synchronize()
+        assert_same(out.to_host(), orc, o.size)
+        assert np.array_equal(crc.cpu().numpy().view(np.uint32), exp_crc), fused
+        assert not bad.cpu().numpy().any()
+    # count pass, then the decode that reuses its counts
+    out = codec.DecodedBlocks(batch.nblk, nr, orc.keys.size, orc.vals.size)
+    codec.count_blocks(batch, out, ws)
+    torch.cuda.synchronize()
+    assert out.totals_host() == (nr, orc.keys.size, orc.vals.size, 0)
+    codec.decode_counted(batch, out, ws)
+    torch.cuda.synchronize()
+    assert_same(out.to_host(), orc, o.size)
+    # positions mode: everything but the values, and every value read through its position
+    out, vp = codec.decode_positions(batch)
+    dev = out.to_host()
+    for f in ("status", "nrec", "rec_base", "key_base", "val_base", "key_end", "val_end", "keys"):
+        assert np.array_equal(getattr(dev, f), getattr(orc, f)), f
+    assert tuple(dev.totals) == (nr, orc.keys.size, orc.vals.size, 0)
+    vu.check_positions(d, o, l, orc, vp.cpu().numpy().view(np.uint32))
+
+
 def _tail_records(rng, n, mode):
     """n strictly increasing keys for the copy waves' key-tail paths, random 0..64 B values.
     "counter": be64 counter with random gaps (shared ~5 B) + a random tail of 0..292 B, so every

@@ -8,8 +8,8 @@ that into its two ingredients:
   * spilling alone is safe: libmtblx_spill.so (-DMTBLX_SPILL, every pipe kernel spills up to
     100 B per lane) passes the whole parity set on the GPU (tests/test_spill_gpu.py);
   * the fault came from the compiler OUTLINING pipe_crc once the kernel ran out of registers:
-    build/libmtblx_crcnoinline.so (-DMTBLX_CRC_NOINLINE, pipe_crc a real call, TileArgs and the
-    LDS buffer passed as generic pointers) faults in PipeLargeV with no spill pad at all.
+    a build with pipe_crc forced out of line (a real call, TileArgs and the LDS buffer passed as
+    generic pointers; since removed) faulted in PipeLargeV with no spill pad at all.
 The product forces pipe_crc inline. This compiles every .hip source to gfx950 assembly and
 checks each kernel's .amdhsa_private_segment_fixed_size (scratch costs bandwidth) and that no
 s_swappc (call) is emitted anywhere, so either regression fails here before it reaches a GPU.
