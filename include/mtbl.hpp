@@ -306,6 +306,15 @@ struct Record {   // a (key, value) pair served by the iterators (views into the
 
 class Reader;
 
+// one query of Reader::scan_batch
+struct ScanQuery {
+  enum Kind { From = 0, Get = 1, Prefix = 2, Range = 3 };   // mtblx_scan_plan's numbering
+  Kind kind = From;
+  Bytes key;                             // the start key / the key / the prefix
+  Bytes key2;                            // Range: the inclusive end
+  std::optional<uint64_t> max_records;   // stop after this many records
+};
+
 // ReaderIntoIter (src/reader.rs:219-405): built by Reader::into_iter (new), iter_from
 // (new_from), iter_prefix (new_get_prefix), iter_range (new_get_range); next() and the
 // mid-iteration seek() (:302-335).  The device seeks and decodes (mtblx_index_seek_batch,
@@ -425,6 +434,15 @@ class Reader {
     return make(ReaderIntoIter::kRange, start, end);
   }
   size_t len() const;   // records the full iteration yields before it ends (decodes the file once)
+  // iter_from / get / iter_prefix / iter_range for a batch of queries in two launches
+  // (mtblx_scan_plan + mtblx_scan_emit): the records of every query, in query order.  Queries the
+  // kernels hand back (MTBLX_SCAN_LARGE: more than max_blocks data blocks; MTBLX_SCAN_FALLBACK) go
+  // through this Reader's own iter_from / iter_prefix / iter_range / get, which throw where the
+  // reference errs or panics; so does every query of a compressed file or an irregular index.
+  // served (may be null): per query, 1 where the kernels answered it.
+  using Records = std::vector<std::pair<Bytes, Bytes>>;
+  std::vector<Records> scan_batch(const std::vector<ScanQuery>& queries, uint32_t max_blocks = 64,
+                                  std::vector<uint8_t>* served = nullptr) const;
 
  private:
   friend class ReaderBuilder;
@@ -435,6 +453,7 @@ class Reader {
     it.init_from(seek_key);
     return it;
   }
+  Records scan_one(const ScanQuery& q) const;   // one query through the iterators
   mtblx_index_seek index_seek(const Bytes& key) const;
   Bytes index_key(size_t i) const {   // separator key of directory entry i
     const uint32_t a = i ? ikend_[i - 1] : 0;
@@ -1149,6 +1168,86 @@ inline std::optional<Bytes> Reader::get(const uint8_t* key, size_t klen) const {
   if (st == MTBLX_GET_NONE) return std::nullopt;
   if (st == MTBLX_GET_ERR) throw Error(MtblError::InvalidBlock);
   throw Panic(st == MTBLX_GET_LOOP ? "Reader::get never returns" : "Reader::get panics");
+}
+
+inline Reader::Records Reader::scan_one(const ScanQuery& q) const {
+  Records out;
+  const uint64_t lim = q.max_records ? *q.max_records : ~0ull;
+  if (q.kind == ScanQuery::Get) {   // Reader::get: at most one record
+    if (lim == 0) return out;
+    if (auto v = get(q.key.data(), q.key.size())) out.emplace_back(q.key, *v);
+    return out;
+  }
+  ReaderIntoIter it = q.kind == ScanQuery::From ? iter_from(q.key)
+                      : q.kind == ScanQuery::Prefix ? iter_prefix(q.key) : iter_range(q.key, q.key2);
+  while (out.size() < lim) {
+    auto r = it.next();
+    if (!r) break;
+    out.emplace_back(r->key_bytes(), r->val_bytes());
+  }
+  return out;
+}
+
+inline std::vector<Reader::Records> Reader::scan_batch(const std::vector<ScanQuery>& qs, uint32_t max_blocks,
+                                                       std::vector<uint8_t>* served) const {
+  using namespace detail;
+  const uint32_t nq = (uint32_t)qs.size();
+  std::vector<Records> out(nq);
+  if (served) served->assign(nq, 0);
+  if (nq == 0) return out;
+  if (meta_.compression_algorithm != 0 || !regular()) {
+    for (uint32_t q = 0; q < nq; ++q) out[q] = scan_one(qs[q]);
+    return out;
+  }
+  Bytes kb, k2b;
+  std::vector<uint64_t> ke(nq), k2e(nq), mr(nq);
+  std::vector<int32_t> type(nq);
+  for (uint32_t q = 0; q < nq; ++q) {
+    type[q] = (int32_t)qs[q].kind;
+    kb.insert(kb.end(), qs[q].key.begin(), qs[q].key.end());
+    if (qs[q].kind == ScanQuery::Range) k2b.insert(k2b.end(), qs[q].key2.begin(), qs[q].key2.end());
+    ke[q] = kb.size();
+    k2e[q] = k2b.size();
+    mr[q] = qs[q].max_records ? *qs[q].max_records : ~0ull;
+  }
+  const DevBuf d_k = upload_key(kb), d_ke = upload(ke.data(), nq), d_k2 = upload_key(k2b), d_k2e = upload(k2e.data(), nq),
+               d_mr = upload(mr.data(), nq);
+  const size_t wsb = mtblx_scan_workspace_bytes(nq);
+  const DevBuf ws(wsb), d_res(sizeof(mtblx_scan_result) * (size_t)nq);   // hipMalloc aligns to 256 bytes
+  uint64_t totals[4];
+  abi_check(mtblx_scan_plan(dfile_.as<uint8_t>(), file_.size(), version_, verify_ ? 1 : 0, index_off_, index_len_,
+                            nullptr, nullptr, nullptr, nullptr, 0, nullptr, type.data(), d_k.as<uint8_t>(),
+                            d_ke.as<uint64_t>(), d_k2.as<uint8_t>(), d_k2e.as<uint64_t>(), d_mr.as<uint64_t>(),
+                            max_blocks, nq, d_res.as<mtblx_scan_result>(), totals, ws.p, wsb, nullptr),
+            "mtblx_scan_plan");
+  const uint64_t nrec = totals[0], kbytes = totals[1], vbytes = totals[2];
+  const DevBuf o_k(kbytes), o_v(vbytes), o_ke(8 * nrec), o_ve(8 * nrec), o_fl(4);
+  const mtblx_scanned so{o_k.as<uint8_t>(), kbytes, o_v.as<uint8_t>(), vbytes, o_ke.as<uint64_t>(), o_ve.as<uint64_t>(),
+                         nrec, o_fl.as<uint32_t>()};
+  abi_check(mtblx_scan_emit(dfile_.as<uint8_t>(), file_.size(), version_, index_off_, index_len_, nullptr, nullptr,
+                            nullptr, nullptr, 0, nullptr, nq, &so, ws.p, wsb, nullptr),
+            "mtblx_scan_emit");
+  hip_check(hipDeviceSynchronize(), "sync");
+  if (download<uint32_t>(o_fl.p, 1)[0] != 0) throw std::runtime_error("mtblx_scan_emit: flags set");
+  const auto res = download<mtblx_scan_result>(d_res.p, nq);
+  const auto hk = download<uint8_t>(o_k.p, kbytes), hv = download<uint8_t>(o_v.p, vbytes);
+  const auto hke = download<uint64_t>(o_ke.p, nrec), hve = download<uint64_t>(o_ve.p, nrec);
+  for (uint32_t q = 0; q < nq; ++q) {
+    const mtblx_scan_result& r = res[q];
+    if (r.status != MTBLX_SCAN_OK) {
+      out[q] = scan_one(qs[q]);
+      continue;
+    }
+    if (served) (*served)[q] = 1;
+    uint64_t pk = r.key_base, pv = r.val_base;
+    out[q].reserve(r.nrec);
+    for (uint64_t i = r.rec_base; i < r.rec_base + r.nrec; ++i) {
+      out[q].emplace_back(Bytes(hk.begin() + pk, hk.begin() + hke[i]), Bytes(hv.begin() + pv, hv.begin() + hve[i]));
+      pk = hke[i];
+      pv = hve[i];
+    }
+  }
+  return out;
 }
 
 // ------------------------------------------------------------------ Merger (src/merger.rs)

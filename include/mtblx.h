@@ -38,7 +38,8 @@ extern "C" {
 
 #define MTBLX_ABI_VERSION 3   /* 3: the block cut takes a caller-owned workspace (round 6).  Still 3 with
                                  mtblx_decode_blocks_valpos / mtblx_pipe_decode_valpos and with the
-                                 mtblx_merge_* and mtblx_sort_* calls: added symbols, no existing one changed */
+                                 mtblx_merge_*, mtblx_sort_* and mtblx_scan_* calls: added symbols, no existing
+                                 one changed */
 
 /* ---- API return codes ---- */
 #define MTBLX_OK 0
@@ -357,6 +358,89 @@ int mtblx_entry_offsets(const uint8_t* block, uint64_t len, uint64_t* offs, uint
  *     min-reduced: set it to n before the call. */
 int mtblx_key_filter(const uint8_t* keys, const uint64_t* key_end, uint64_t n, int32_t type, const uint8_t* k,
                      uint64_t klen, uint64_t* first_fail, void* stream);
+
+/* ---- batched scans: iter_from / get / iter_prefix / iter_range for nq queries at once ----
+ * Per query the whole ReaderIntoIter loop (new_from + next(), src/reader.rs:256-405) runs on the
+ * device: the index seek on a fresh iterator, Reader::block (framing, checksum when verify, the
+ * caller's decompressed-block table as mtblx_get_decompressed), BlockIter::seek(start), records
+ * while the stop rule holds (Get: == k, GetPrefix: starts_with(k), GetRange: <= k2), and at a
+ * block's end the next index entry's block from its first record.
+ *
+ * Two calls, as the Merger.  mtblx_scan_plan (synchronous) walks every query once without writing
+ * a record, counts it, scans the counts of the OK queries in query order into per-query output
+ * offsets and returns the totals.  mtblx_scan_emit (asynchronous) walks the OK queries again from
+ * the landing the plan saved and writes their records.  The caller owns the workspace (device,
+ * 256-byte aligned, mtblx_scan_workspace_bytes; no fill needed; one call at a time).
+ *
+ * Per query, res[q].status:
+ *   MTBLX_SCAN_OK        the records are in the output; the iteration ended with None (end = 0) or
+ *                        at max_records[q] (end = 1).
+ *   MTBLX_SCAN_LARGE     the iteration would open more than max_blocks data blocks (every
+ *                        Reader::block call counts, the sought block included).  Counts 0, nothing
+ *                        emitted: a scan of many blocks belongs to the full-rate decoder.
+ *   MTBLX_SCAN_FALLBACK  anything else: the reference would panic, return Err or never return
+ *                        somewhere on this query's path (a checksum mismatch with verify included),
+ *                        a block content >= 4 GiB, a compressed block missing from the table, or a
+ *                        key longer than MTBLX_SCAN_MAX_KEY bytes among the entries the walk parses.
+ *                        Counts 0, nothing emitted: the caller runs the query through the exact
+ *                        seek primitives above, which keep every such quirk.
+ * Corrupt files read with verify = 0 are supported input: every such condition is detected and no
+ * access leaves the file, the table's blocks, the workspace or the outputs.
+ *
+ * type (HOST array [nq]): 0 from, 1 get, 2 prefix, 3 range -- mtblx_key_filter's numbering; get is
+ * Reader::get (src/reader.rs:111-122), which takes the iterator's first record only.  keys /
+ * key_end (device, u64 END offsets): the start key / prefix of query q.  keys2 / key2_end (device):
+ * the inclusive range end, read only for type 3; both may be NULL when no query is a range.
+ * max_records (device [nq], may be NULL = no limit).  res: device [nq].  totals: host [4] = records,
+ * key bytes, value bytes of the OK queries, and the number of queries not OK.
+ *
+ * MTBLX_E_INVAL before any device call: NULL or misaligned workspace, ws_bytes too small, a type
+ * outside 0..3, version > 1, a NULL required pointer.  nq == 0: MTBLX_OK with zero totals. */
+#define MTBLX_SCAN_OK 0
+#define MTBLX_SCAN_LARGE 1
+#define MTBLX_SCAN_FALLBACK 2
+#define MTBLX_SCAN_MAX_KEY 1024          /* bytes of the emit kernel's per-wave key buffer (LDS)      */
+#define MTBLX_SCAN_OVERFLOW 1u           /* *flags of mtblx_scan_emit: a capacity was too small; no
+                                            record that does not fit whole is written               */
+#define MTBLX_SCAN_NOT_PLANNED 2u        /* *flags: the workspace is not that of a mtblx_scan_plan of
+                                            nq queries; nothing was written                         */
+#define MTBLX_SCAN_INTERNAL 4u           /* *flags: the emit walk met a count that differs from the
+                                            plan's (a bug); it never writes outside the query's slot */
+typedef struct mtblx_scan_result {
+  int32_t status;                          /* MTBLX_SCAN_*                                          */
+  int32_t end;                             /* OK: 0 = the iterator returned None, 1 = max_records   */
+  uint64_t nrec, key_bytes, val_bytes;     /* of this query (0 unless OK)                           */
+  uint64_t rec_base, key_base, val_base;   /* exclusive offsets of this query into the outputs: the
+                                              scan of the three counts over the OK queries before it */
+  uint32_t blocks;                         /* data blocks opened                                    */
+  uint32_t pad;
+} mtblx_scan_result;
+/* Output of mtblx_scan_emit (device buffers; keys_cap / vals_cap in bytes, rec_cap in records).
+ * key_end / val_end are u64 END offsets counted from record 0 of the whole batch: keys, key_end,
+ * vals, val_end and n = totals[0] are an mtblx_records as they stand; query q's records are
+ * [rec_base, rec_base + nrec). */
+typedef struct mtblx_scanned {
+  uint8_t* keys;
+  uint64_t keys_cap;
+  uint8_t* vals;
+  uint64_t vals_cap;
+  uint64_t* key_end;
+  uint64_t* val_end;
+  uint64_t rec_cap;
+  uint32_t* flags;                         /* device u32, written by the emit: MTBLX_SCAN_* bits   */
+} mtblx_scanned;
+size_t mtblx_scan_workspace_bytes(uint32_t nq);
+int mtblx_scan_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify, uint64_t index_off,
+                    uint64_t index_len, const uint64_t* tab_start, const uint64_t* tab_doff, const uint64_t* tab_dlen,
+                    const int32_t* tab_st, uint32_t ntab, const uint8_t* dec, const int32_t* type,
+                    const uint8_t* keys, const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
+                    const uint64_t* max_records, uint32_t max_blocks, uint32_t nq, mtblx_scan_result* res,
+                    uint64_t* totals, void* workspace, size_t ws_bytes, void* stream);
+/* dec == NULL: the file is not compressed (the table arguments are ignored). */
+int mtblx_scan_emit(const uint8_t* file, uint64_t file_len, uint32_t version, uint64_t index_off, uint64_t index_len,
+                    const uint64_t* tab_start, const uint64_t* tab_doff, const uint64_t* tab_dlen,
+                    const int32_t* tab_st, uint32_t ntab, const uint8_t* dec, uint32_t nq, const mtblx_scanned* out,
+                    const void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- encode side on the device: Writer's block cut + BlockBuilder + write_block framing ----
  * Records (device): key r = keys[r ? key_end[r-1] : 0 .. key_end[r]), value likewise (u64 END

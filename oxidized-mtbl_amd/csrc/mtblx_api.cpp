@@ -199,6 +199,69 @@ extern "C" int mtblx_sort_emit(const mtblx_records* in, int mode, const mtblx_me
   return mtblx_sort_impl_emit(in, mode, out, ws, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- batched scans (csrc/scan.hip): the argument checks need no device ----
+extern "C" size_t mtblx_scan_impl_ws_bytes(uint32_t nq);
+extern "C" int mtblx_scan_impl_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
+                                    uint64_t index_off, uint64_t index_len, const uint64_t* tab_start,
+                                    const uint64_t* tab_doff, const uint64_t* tab_dlen, const int32_t* tab_st,
+                                    uint32_t ntab, const uint8_t* dec, const int32_t* type, const uint8_t* keys,
+                                    const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
+                                    const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
+                                    mtblx_scan_result* res, uint64_t* totals, void* ws, hipStream_t s);
+extern "C" int mtblx_scan_impl_emit(const uint8_t* file, uint64_t file_len, uint32_t version, uint64_t index_off,
+                                    uint64_t index_len, const uint64_t* tab_start, const uint64_t* tab_doff,
+                                    const uint64_t* tab_dlen, const int32_t* tab_st, uint32_t ntab,
+                                    const uint8_t* dec, uint32_t nq, const mtblx_scanned* out, const void* ws,
+                                    hipStream_t s);
+
+extern "C" size_t mtblx_scan_workspace_bytes(uint32_t nq) { return mtblx_scan_impl_ws_bytes(nq); }
+
+static int scan_check(const uint8_t* file, uint32_t version, const uint64_t* tab_start, const uint64_t* tab_doff,
+                      const uint64_t* tab_dlen, const int32_t* tab_st, uint32_t ntab, const uint8_t* dec, uint32_t nq,
+                      const void* ws, size_t wsb) {
+  if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0 || wsb < mtblx_scan_impl_ws_bytes(nq)) return MTBLX_E_INVAL;
+  if (version > 1) return MTBLX_E_INVAL;
+  if (nq && !file) return MTBLX_E_INVAL;
+  if (dec && ntab && (!tab_start || !tab_doff || !tab_dlen || !tab_st)) return MTBLX_E_INVAL;
+  return MTBLX_OK;
+}
+
+extern "C" int mtblx_scan_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify, uint64_t index_off,
+                               uint64_t index_len, const uint64_t* tab_start, const uint64_t* tab_doff,
+                               const uint64_t* tab_dlen, const int32_t* tab_st, uint32_t ntab, const uint8_t* dec,
+                               const int32_t* type, const uint8_t* keys, const uint64_t* key_end, const uint8_t* keys2,
+                               const uint64_t* key2_end, const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
+                               mtblx_scan_result* res, uint64_t* totals, void* ws, size_t wsb, void* stream) {
+  if (!totals) return MTBLX_E_INVAL;
+  const int c = scan_check(file, version, tab_start, tab_doff, tab_dlen, tab_st, ntab, dec, nq, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  if (nq && (!type || !keys || !key_end || !res)) return MTBLX_E_INVAL;
+  for (uint32_t q = 0; q < nq; ++q) {
+    if (type[q] < 0 || type[q] > 3) return MTBLX_E_INVAL;
+    if (type[q] == 3 && (!keys2 || !key2_end)) return MTBLX_E_INVAL;
+  }
+  memset(totals, 0, 4 * sizeof(uint64_t));
+  if (nq == 0) return MTBLX_OK;
+  return mtblx_scan_impl_plan(file, file_len, version, verify, index_off, index_len, tab_start, tab_doff, tab_dlen,
+                              tab_st, ntab, dec, type, keys, key_end, keys2, key2_end, max_records, max_blocks, nq, res,
+                              totals, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mtblx_scan_emit(const uint8_t* file, uint64_t file_len, uint32_t version, uint64_t index_off,
+                               uint64_t index_len, const uint64_t* tab_start, const uint64_t* tab_doff,
+                               const uint64_t* tab_dlen, const int32_t* tab_st, uint32_t ntab, const uint8_t* dec,
+                               uint32_t nq, const mtblx_scanned* out, const void* ws, size_t wsb, void* stream) {
+  if (!out || !out->flags) return MTBLX_E_INVAL;
+  if ((!out->keys && out->keys_cap) || (!out->vals && out->vals_cap) ||
+      ((!out->key_end || !out->val_end) && out->rec_cap))
+    return MTBLX_E_INVAL;
+  const int c = scan_check(file, version, tab_start, tab_doff, tab_dlen, tab_st, ntab, dec, nq, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  if (nq == 0) return MTBLX_OK;
+  return mtblx_scan_impl_emit(file, file_len, version, index_off, index_len, tab_start, tab_doff, tab_dlen, tab_st,
+                              ntab, dec, nq, out, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
 // ---- bounds-checked diagnostic build only (csrc/bounds.h, Makefile target `bounds`) ----
 #ifdef MTBLX_BOUNDS
 #include <stdio.h>

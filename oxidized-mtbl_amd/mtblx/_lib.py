@@ -46,6 +46,7 @@ EXPORTS = [
     "mtblx_sort_workspace_bytes", "mtblx_sort_plan", "mtblx_sort_emit", "mtblx_sort_plan_timed",
     "mtblx_snappy_compress_workspace_bytes", "mtblx_snappy_slots", "mtblx_snappy_compress_dev", "mtblx_frame_blocks",
     "mtblx_encode_index_c",
+    "mtblx_scan_workspace_bytes", "mtblx_scan_plan", "mtblx_scan_emit",
 ]
 MERGE_MAX_SOURCES, MERGE_MAX_RECORDS = 64, (1 << 32) - 16
 MERGE_GROUPS, MERGE_CONCAT, MERGE_FIRST, MERGE_LAST = range(4)
@@ -53,6 +54,10 @@ MERGE_UNSORTED, MERGE_INTERNAL = 1, 2          # totals[5] of mtblx_merge_plan
 MERGE_OVERFLOW, MERGE_NOT_PLANNED = 1, 2       # *flags of mtblx_merge_emit
 SORT_TILE = 1024                               # MTBLX_SORT_TILE: handles per tile-sorted run of mtblx_sort_plan
 PLAN_OUT_OF_ORDER, PLAN_PANIC, PLAN_TOO_LONG = 1, 2, 4
+SCAN_OK, SCAN_LARGE, SCAN_FALLBACK = range(3)  # mtblx_scan_result.status
+SCAN_MAX_KEY = 1024                            # MTBLX_SCAN_MAX_KEY: the emit kernel's key buffer
+SCAN_OVERFLOW, SCAN_NOT_PLANNED, SCAN_INTERNAL = 1, 2, 4   # *flags of mtblx_scan_emit
+SCAN_FROM, SCAN_GET, SCAN_PREFIX, SCAN_RANGE = range(4)    # query types (mtblx_key_filter's numbering)
 
 
 class BlockBatch(C.Structure):
@@ -76,6 +81,17 @@ class Merged(C.Structure):   # mtblx_merged (capacities in bytes)
     _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("key_end", C.c_void_p), ("key_end_cap", C.c_uint64),
                 ("vals", C.c_void_p), ("vals_cap", C.c_uint64), ("val_end", C.c_void_p), ("val_end_cap", C.c_uint64),
                 ("grp_end", C.c_void_p), ("grp_end_cap", C.c_uint64), ("flags", C.c_void_p)]
+
+
+class ScanResult(C.Structure):   # mtblx_scan_result
+    _fields_ = [("status", C.c_int32), ("end", C.c_int32), ("nrec", C.c_uint64), ("key_bytes", C.c_uint64),
+                ("val_bytes", C.c_uint64), ("rec_base", C.c_uint64), ("key_base", C.c_uint64),
+                ("val_base", C.c_uint64), ("blocks", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class Scanned(C.Structure):   # mtblx_scanned (keys_cap / vals_cap in bytes, rec_cap in records)
+    _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("vals", C.c_void_p), ("vals_cap", C.c_uint64),
+                ("key_end", C.c_void_p), ("val_end", C.c_void_p), ("rec_cap", C.c_uint64), ("flags", C.c_void_p)]
 
 
 class PipeStats(C.Structure):
@@ -287,6 +303,17 @@ def lib() -> C.CDLL:
         L.mtblx_sort_emit.argtypes = [C.POINTER(Records), C.c_int, C.POINTER(Merged), C.c_void_p, C.c_size_t,
                                       C.c_void_p]
         L.mtblx_sort_emit.restype = C.c_int
+        L.mtblx_scan_workspace_bytes.argtypes = [C.c_uint32]
+        L.mtblx_scan_workspace_bytes.restype = C.c_size_t
+        _file = [C.c_void_p, C.c_uint64, C.c_uint32]                                    # file, file_len, version
+        _tab = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]  # tab_*, ntab, dec
+        L.mtblx_scan_plan.argtypes = _file + [C.c_int, C.c_uint64, C.c_uint64] + _tab + [
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+            C.c_void_p, u64p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_scan_plan.restype = C.c_int
+        L.mtblx_scan_emit.argtypes = _file + [C.c_uint64, C.c_uint64] + _tab + [
+            C.c_uint32, C.POINTER(Scanned), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_scan_emit.restype = C.c_int
         L.mtblx_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_uint64]
         L.mtblx_host_alloc.restype = C.c_int
         L.mtblx_host_free.argtypes = [C.c_void_p]

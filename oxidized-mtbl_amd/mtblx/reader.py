@@ -76,6 +76,54 @@ class Scan:
         return out
 
 
+class ScanBatch:
+    """Reader.scan_batch's result.  Device tensors: `keys` / `vals` (the records of the queries the
+    kernels served, in query order), `key_end` / `val_end` (int64 END offsets from record 0 of the
+    batch: with keys / vals an mtblx_records), `rec_off` (int64 [nq + 1]: query q's records are
+    [rec_off[q], rec_off[q + 1])), `status` (int32 [nq], SCAN_*).  Queries that are not SCAN_OK were
+    answered by iterator.bulk(); scan(q) / records(q) give every query's result, whichever path
+    served it."""
+
+    def __init__(self, nq, keys, vals, key_end, val_end, rec_off, status, host, served):
+        self.nq, self.keys, self.vals, self.key_end, self.val_end = nq, keys, vals, key_end, val_end
+        self.rec_off, self.status = rec_off, status
+        self._res = host           # mtblx_scan_result per query (host)
+        self._served = served      # q -> Scan of the queries bulk() answered
+        self._host = None
+        self.n_large = int((host["status"] == _lib.SCAN_LARGE).sum())
+        self.n_fallback = int((host["status"] == _lib.SCAN_FALLBACK).sum())
+
+    def served_by_kernel(self, q: int) -> bool:
+        return q not in self._served
+
+    def scan(self, q: int) -> Scan:
+        """query q as iter_from / iter_prefix / iter_range would return it"""
+        if q in self._served:
+            return self._served[q]
+        r = self._res[q]
+        r0, n = int(r["rec_base"]), int(r["nrec"])
+        k0, v0 = int(r["key_base"]), int(r["val_base"])
+        return Scan(END_NONE, "None", n, self.keys[k0: k0 + int(r["key_bytes"])],
+                    self.vals[v0: v0 + int(r["val_bytes"])], self.key_end[r0: r0 + n] - k0,
+                    self.val_end[r0: r0 + n] - v0)
+
+    def records(self, q: int):
+        """query q's (key, value) pairs on the host (the batch is copied once)"""
+        if q in self._served:
+            return self._served[q].records()
+        if self._host is None:
+            self._host = (self.keys.cpu().numpy().tobytes(), self.vals.cpu().numpy().tobytes(),
+                          self.key_end.cpu().numpy(), self.val_end.cpu().numpy())
+        k, v, ke, ve = self._host
+        r = self._res[q]
+        r0, pk, pv = int(r["rec_base"]), int(r["key_base"]), int(r["val_base"])
+        out = []
+        for i in range(r0, r0 + int(r["nrec"])):
+            out.append((k[pk: ke[i]], v[pv: ve[i]]))
+            pk, pv = int(ke[i]), int(ve[i])
+        return out
+
+
 class ReaderBuilder:
     """src/reader.rs:15-30: verify_checksums defaults to true."""
 
@@ -564,6 +612,130 @@ class Reader:
         """Reader::iter_range (src/reader.rs:136-138): start <= key <= end"""
         from . import iterator
         return iterator.bulk(self, "range", bytes(start), bytes(end))
+
+    # ------------------------------------------------------------------ batched scans
+    def _scan_plan(self, queries, max_blocks, max_records, stream):
+        """mtblx_scan_plan over `queries` -> (res uint8 [nq * 64] device, totals, workspace, per-query
+        limits, table arguments)"""
+        from . import iterator
+        dev = self.file.device
+        nq = len(queries)
+        qs = []
+        for q in queries:
+            kind = q[0]
+            if kind not in ("from", "get", "prefix", "range") or len(q) != (3 if kind == "range" else 2):
+                raise ValueError(f"scan_batch: bad query {q!r}")
+            qs.append((iterator.KINDS[kind], bytes(q[1]), bytes(q[2]) if kind == "range" else b""))
+        if max_records is None or isinstance(max_records, int):
+            limits = [max_records] * nq
+        else:
+            limits = list(max_records)
+            if len(limits) != nq:
+                raise ValueError("scan_batch: max_records must be one value or one per query")
+        if any(m is not None and m < 0 for m in limits):
+            raise ValueError("scan_batch: negative max_records")
+
+        def blob(ks):
+            b = torch.frombuffer(bytearray(b"".join(ks) or b"\0"), dtype=torch.uint8).to(dev)
+            e = torch.from_numpy(np.cumsum([len(k) for k in ks] or [0], dtype=np.int64)).to(dev)
+            return b, e
+
+        kb, ke = blob([k for _, k, _ in qs])
+        k2b, k2e = blob([k2 for _, _, k2 in qs])
+        types = np.ascontiguousarray([t for t, _, _ in qs] or [0], dtype=np.int32)
+        mr = None
+        if any(m is not None for m in limits):
+            mr = torch.from_numpy(np.array([(1 << 63) - 1 if m is None else min(m, (1 << 63) - 1) for m in limits],
+                                           dtype=np.int64)).to(dev)
+        L = _lib.lib()
+        wsb = int(L.mtblx_scan_workspace_bytes(nq))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)       # the caching allocator aligns to 512 bytes
+        res = torch.zeros(max(nq, 1) * C.sizeof(_lib.ScanResult), dtype=torch.uint8, device=dev)
+        if self.compression == 0:
+            tab = (None, None, None, None, 0, None)
+            keep = None
+        else:
+            keep = self._dec_table()
+            ts, tdo, tdl, tst, ntab, dec = keep
+            tab = (C.c_void_p(ts.data_ptr()), C.c_void_p(tdo.data_ptr()), C.c_void_p(tdl.data_ptr()),
+                   C.c_void_p(tst.data_ptr()), ntab, C.c_void_p(dec.data_ptr()))
+        totals = (C.c_uint64 * 4)()
+        rc = L.mtblx_scan_plan(C.c_void_p(self.file.data_ptr()), self.len, self.version, 1 if self.verify else 0,
+                               self.index_off, self.index_len, *tab, C.c_void_p(types.ctypes.data),
+                               C.c_void_p(kb.data_ptr()), C.c_void_p(ke.data_ptr()), C.c_void_p(k2b.data_ptr()),
+                               C.c_void_p(k2e.data_ptr()), C.c_void_p(mr.data_ptr()) if mr is not None else None,
+                               max_blocks, nq, C.c_void_p(res.data_ptr()), totals, C.c_void_p(ws.data_ptr()), wsb,
+                               C.c_void_p(codec._stream_handle(stream)))
+        if rc != 0:
+            raise RuntimeError(f"mtblx_scan_plan failed: {rc}")
+        return res, [int(x) for x in totals], ws, wsb, limits, tab, keep
+
+    def count_batch(self, queries, max_blocks: int = 64, stream=None):
+        """The plan of scan_batch alone: (status int32, nrec, key_bytes, val_bytes int64) [nq] on the
+        device.  Queries that are not SCAN_OK count 0: scan_batch answers them through bulk()."""
+        nq = len(queries)
+        res = self._scan_plan(queries, max_blocks, None, stream)[0]
+        w = res.view(torch.int64).view(-1, 8)[:nq]
+        return res.view(torch.int32).view(-1, 16)[:nq, 0], w[:, 1], w[:, 2], w[:, 3]
+
+    def scan_batch(self, queries, max_blocks: int = 64, max_records=None, stream=None) -> "ScanBatch":
+        """iter_from / get / iter_prefix / iter_range for a batch of queries: one plan, one allocation
+        sized from its totals, one emit (mtblx_scan_plan / mtblx_scan_emit).  `queries`: ("from", k),
+        ("get", k), ("prefix", p) or ("range", a, b); `max_records`: None, one limit, or one per query
+        (None = no limit).  A query the kernels hand back -- SCAN_LARGE: more than `max_blocks` data
+        blocks; SCAN_FALLBACK: somewhere the reference panics, errs or loops -- is answered by
+        iterator.bulk() with the limit applied; so is every query when the index block is not
+        regular.  ("get", k) is Reader::get: at most one record."""
+        from . import iterator
+        dev = self.file.device
+        queries = list(queries)
+        nq = len(queries)
+
+        def limited(q, m):
+            kind = queries[q][0]
+            s = iterator.bulk(self, kind, bytes(queries[q][1]), bytes(queries[q][2]) if kind == "range" else b"")
+            if kind == "get":
+                m = 1 if m is None else min(m, 1)
+            if m is None or s.nrec < m or (m == 0 and s.end != END_NONE):
+                return s
+            p = iterator._cut_part((s.keys, s.vals, s.key_end, s.val_end, s.nrec), m)
+            return Scan(END_NONE, "None", m, p[0], p[1], p[2], p[3])
+
+        z8 = torch.zeros(0, dtype=torch.uint8, device=dev)
+        z64 = torch.zeros(0, dtype=torch.int64, device=dev)
+        if nq == 0 or not self.index_regular():
+            limits = [max_records] * nq if max_records is None or isinstance(max_records, int) else list(max_records)
+            served = {q: limited(q, limits[q]) for q in range(nq)}
+            host = np.zeros(nq, np.dtype(_lib.ScanResult))
+            host["status"] = _lib.SCAN_FALLBACK
+            return ScanBatch(nq, z8, z8, z64, z64, torch.zeros(nq + 1, dtype=torch.int64, device=dev),
+                             torch.full((nq,), _lib.SCAN_FALLBACK, dtype=torch.int32, device=dev), host, served)
+        res, totals, ws, wsb, limits, tab, keep = self._scan_plan(queries, max_blocks, max_records, stream)
+        nrec, kbytes, vbytes = totals[0], totals[1], totals[2]
+        buf = torch.empty(kbytes + vbytes + 16 * nrec + 8, dtype=torch.uint8, device=dev)   # ends first: aligned
+        key_end = buf[: 8 * nrec].view(torch.int64)
+        val_end = buf[8 * nrec: 16 * nrec].view(torch.int64)
+        flags = buf[16 * nrec: 16 * nrec + 8].view(torch.int32)
+        keys = buf[16 * nrec + 8: 16 * nrec + 8 + kbytes]
+        vals = buf[16 * nrec + 8 + kbytes:]
+        out = _lib.Scanned(keys=buf.data_ptr() + 16 * nrec + 8, keys_cap=kbytes,
+                           vals=buf.data_ptr() + 16 * nrec + 8 + kbytes, vals_cap=vbytes,
+                           key_end=buf.data_ptr(), val_end=buf.data_ptr() + 8 * nrec, rec_cap=nrec,
+                           flags=buf.data_ptr() + 16 * nrec)
+        rc = _lib.lib().mtblx_scan_emit(C.c_void_p(self.file.data_ptr()), self.len, self.version, self.index_off,
+                                        self.index_len, *tab, nq, C.byref(out), C.c_void_p(ws.data_ptr()), wsb,
+                                        C.c_void_p(codec._stream_handle(stream)))
+        if rc != 0:
+            raise RuntimeError(f"mtblx_scan_emit failed: {rc}")
+        host = np.frombuffer(res.cpu().numpy().tobytes(), np.dtype(_lib.ScanResult))[:nq]   # the one read-back
+        fl = int(flags[0].item())
+        if fl:
+            raise RuntimeError(f"mtblx_scan_emit: flags {fl}")
+        w = res.view(torch.int64).view(-1, 8)[:nq]
+        rec_off = torch.cat([w[:, 4], torch.tensor([nrec], dtype=torch.int64, device=dev)])
+        status = res.view(torch.int32).view(-1, 16)[:nq, 0]
+        served = {int(q): limited(int(q), limits[int(q)]) for q in np.nonzero(host["status"] != _lib.SCAN_OK)[0]}
+        return ScanBatch(nq, keys, vals, key_end, val_end, rec_off, status, host, served)
 
     def into_iter(self, kind: str = "iter", key: bytes = b"", key2: bytes = b""):
         """the stateful ReaderIntoIter (next() / seek()), see iterator.ReaderIntoIter"""
