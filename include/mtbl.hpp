@@ -892,7 +892,9 @@ inline ReaderIntoIter::EmitResult ReaderIntoIter::emit(const Content& c, const B
       hip_check(hipDeviceSynchronize(), "sync");
     }
     b.vals = download<uint8_t>(d_v.p, r.res.val_bytes);
-    if (r.res.has_val) b.last_val = download<uint8_t>(c.base + c.off + r.res.last_voff, r.res.last_vlen);
+    // (a corrupt entry's value may run past the content: ReaderIntoGet could not slice it either)
+    if (r.res.has_val && r.res.last_voff <= c.len && r.res.last_vlen <= c.len - r.res.last_voff)
+      b.last_val = download<uint8_t>(c.base + c.off + r.res.last_voff, r.res.last_vlen);
     return r;
   }
   throw std::runtime_error("mtblx_block_seek_batch: output sizes did not converge");
@@ -1153,7 +1155,8 @@ inline std::optional<Bytes> Reader::get(const uint8_t* key, size_t klen) const {
     }
   }
   const uint64_t kend = klen;
-  DevBuf d_key = upload(key, klen ? klen : 1), d_kend = upload(&kend, 1);
+  static const uint8_t zero = 0;   // the empty key: one readable byte (key may be null)
+  DevBuf d_key = klen ? upload(key, klen) : upload(&zero, 1), d_kend = upload(&kend, 1);
   DevBuf d_st(4), d_vo(8), d_vl(8);
   abi_check(mtblx_get(dfile_.as<uint8_t>(), file_.size(), version_, verify_ ? 1 : 0, index_off_, index_len_,
                       d_key.as<uint8_t>(), d_kend.as<uint64_t>(), 1, d_st.as<int32_t>(), d_vo.as<uint64_t>(),
