@@ -443,6 +443,10 @@ class Reader {
   using Records = std::vector<std::pair<Bytes, Bytes>>;
   std::vector<Records> scan_batch(const std::vector<ScanQuery>& queries, uint32_t max_blocks = 64,
                                   std::vector<uint8_t>* served = nullptr) const;
+  // blocks this Reader has decompressed on the host so far (Zlib / Zstd; a Snappy file's blocks are
+  // decompressed on the device when the iterator loads them, and on the host only by a seek's own
+  // block and by blocks >= 4 GiB)
+  uint64_t host_decompressed_blocks() const { return host_dec_blocks_; }
 
  private:
   friend class ReaderBuilder;
@@ -497,6 +501,7 @@ class Reader {
   mutable std::vector<uint64_t> eoffs_;
   mutable bool eoffs_known_ = false, regular_ = false;
   mutable std::optional<size_t> len_;
+  mutable uint64_t host_dec_blocks_ = 0;
 };
 
 class ReaderBuilder {   // src/reader.rs:15-30
@@ -631,12 +636,39 @@ inline std::vector<ReaderIntoIter::Loaded> Reader::load_framed(const Framing& f)
   std::vector<uint32_t> ul(n, 0);
   std::vector<uint64_t> ulen(n, 0);
   Decoded dec;
-  if (meta_.compression_algorithm != 0) {
+  if (meta_.compression_algorithm == 1 && n) {
+    // Snappy: the stored bytes stay on the device (mtblx_stage_plan / _emit); a preamble is a u32, so
+    // no decompressed content here is >= 4 GiB
+    DevBuf d_st = upload(f.st.data(), n), d_bad = upload(bad.data(), n);
+    const size_t wsb = mtblx_stage_workspace_bytes(n);
+    DevBuf ws(wsb);
+    uint64_t tot[3] = {0, 0, 0};
+    abi_check(mtblx_stage_plan(dfile_.as<uint8_t>(), file_.size(), d_o, d_l2.as<uint32_t>(), d_st.as<int32_t>(),
+                               d_bad.as<uint8_t>(), n, nullptr, 0, tot, ws.p, wsb, nullptr),
+              "mtblx_stage_plan");
+    ubuf = std::make_shared<DevBuf>(tot[0] + 16);
+    DevBuf d_uo(8ull * n), d_ul(4ull * n), t0(8ull * n), t1(8ull * n), t2(8ull * n), t3(4ull * n);
+    abi_check(mtblx_stage_emit(dfile_.as<uint8_t>(), file_.size(), d_o, n, nullptr, 0, ubuf->as<uint8_t>(), tot[0] + 16, 0,
+                               tot[0], (uint32_t)tot[1], d_uo.as<uint64_t>(), d_ul.as<uint32_t>(), t0.as<uint64_t>(),
+                               t1.as<uint64_t>(), t2.as<uint64_t>(), t3.as<int32_t>(), 0, ws.p, wsb, nullptr),
+              "mtblx_stage_emit");
+    hip_check(hipDeviceSynchronize(), "sync");
+    uoff = download<uint64_t>(d_uo.p, n);
+    ul = download<uint32_t>(d_ul.p, n);
+    const std::vector<int32_t> zst = download<int32_t>(t3.p, n);
+    uint32_t umx = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      zerr[i] = zst[i] != 0;
+      ulen[i] = ul[i];
+      umx = std::max(umx, ul[i]);
+    }
+    dec = decode_batch(ubuf->as<uint8_t>(), tot[0] + 16, d_uo.as<uint64_t>(), d_ul.as<uint32_t>(), n, umx);
+  } else if (meta_.compression_algorithm != 0) {
     std::vector<uint64_t> so(n, 0);
     std::vector<uint32_t> sn(n, 0);
     std::vector<int32_t> zst(n, 0);
     for (uint32_t i = 0; i < n; ++i)
-      if (f.st[i] == MTBLX_DIR_OK && !bad[i]) { so[i] = f.off[i]; sn[i] = f.len[i]; }
+      if (f.st[i] == MTBLX_DIR_OK && !bad[i]) { so[i] = f.off[i]; sn[i] = f.len[i]; ++host_dec_blocks_; }
     uint8_t* hb = nullptr;
     mtblx_decompress_blocks(static_cast<uint32_t>(meta_.compression_algorithm), file_.data(), so.data(), sn.data(), n,
                             16, &hb, uoff.data(), ulen.data(), zst.data());
@@ -707,6 +739,7 @@ inline void Reader::load_big(uint64_t boff, ReaderIntoIter::Loaded& L) const {
   }
   uint8_t* hb = nullptr;   // src/reader.rs:166-170 on the host, any size
   uint64_t un = 0;
+  ++host_dec_blocks_;
   if (mtblx_decompress(static_cast<uint32_t>(meta_.compression_algorithm), file_.data() + coff, clen, &hb, &un) !=
       MTBLX_CODEC_OK) {
     if (hb) mtblx_free(hb);
@@ -798,6 +831,7 @@ inline ReaderIntoIter::Content Reader::value_content(const Bytes& value) const {
   if (meta_.compression_algorithm == 0) return ReaderIntoIter::Content{nullptr, dfile_.as<uint8_t>(), coff, clen};
   uint8_t* out = nullptr;
   uint64_t n = 0;
+  ++host_dec_blocks_;
   if (mtblx_decompress(static_cast<uint32_t>(meta_.compression_algorithm), file_.data() + coff, clen, &out, &n) !=
       MTBLX_CODEC_OK)
     throw Error(MtblError::Io);
@@ -817,6 +851,7 @@ inline ReaderIntoIter::Content Reader::seek_content(const mtblx_index_seek& s) c
   // compressed: decompress on the host, Block::init runs on the result (mtblx_block_seek_batch)
   uint8_t* out = nullptr;
   uint64_t n = 0;
+  ++host_dec_blocks_;
   if (mtblx_decompress(static_cast<uint32_t>(meta_.compression_algorithm), file_.data() + s.data_off, s.data_len, &out,
                        &n) != MTBLX_CODEC_OK)
     throw Error(MtblError::Io);

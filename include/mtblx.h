@@ -38,8 +38,8 @@ extern "C" {
 
 #define MTBLX_ABI_VERSION 3   /* 3: the block cut takes a caller-owned workspace (round 6).  Still 3 with
                                  mtblx_decode_blocks_valpos / mtblx_pipe_decode_valpos and with the
-                                 mtblx_merge_*, mtblx_sort_* and mtblx_scan_* calls: added symbols, no existing
-                                 one changed */
+                                 mtblx_merge_*, mtblx_sort_*, mtblx_scan_* and mtblx_stage_* calls: added symbols,
+                                 no existing one changed */
 
 /* ---- API return codes ---- */
 #define MTBLX_OK 0
@@ -723,6 +723,79 @@ int mtblx_snappy_dir(const uint8_t* src, const uint64_t* src_off, const uint32_t
 int mtblx_snappy_decompress_dev(const uint8_t* src, const uint64_t* src_off, const uint32_t* src_len, uint32_t nblk,
                                 uint8_t* dst, const uint64_t* dst_off, const uint32_t* dst_len, uint32_t max_dst_len,
                                 int32_t* status, uint32_t* dec_len, void* stream);
+
+/* ---- device staging of Snappy blocks: a block directory -> a staged batch and a lookup table ----
+ * Reader::block's decompress step (src/reader.rs:166-170) for the entries of a directory as
+ * mtblx_block_dir writes it (blk_off / blk_len / dir_st, device [ndir]), with the stored bytes left
+ * where they are in `file` (device).  bad (device [ndir], may be NULL): the checksum assert of
+ * mtblx_crc32c_blocks (framed).  sel (device [nsel], may be NULL = every entry, n = ndir): ascending
+ * directory ordinals; n = nsel entries are staged.  Two calls, as the Merger and the scans:
+ *
+ * mtblx_stage_plan (synchronous): an entry that is not MTBLX_DIR_OK, is `bad`, names an ordinal
+ * >= ndir or an extent outside the file is SKIPPED -- the reference panics before it decompresses
+ * it -- and gets length 0 and no error.  The other entries' preambles give 16-byte aligned
+ * destinations (mtblx_snappy_dir).  totals (host [3]) = bytes of the layout, the largest
+ * decompressed length, corrupt preambles among the entries not skipped.  A stored length of 0 is a
+ * corrupt preamble (the host stage's Err(Io), mtblx_decompress_blocks).
+ *
+ * mtblx_stage_emit (asynchronous, no allocation, no synchronisation): decompresses entry j into
+ * dst[base + its offset ..) with mtblx_snappy_decompress_dev's kernels and variant choice
+ * (max_dec_len = totals[1]); base % 16 == 0 and base + total <= dst_cap (total = totals[0]), else
+ * MTBLX_E_INVAL.  Writes
+ *   dst_off / dec_len (device [n], either may be NULL): with dst, an mtblx_block_batch directory of
+ *     the decompressed blocks; dec_len 0 for a failed or skipped entry;
+ *   tab_start / tab_doff / tab_dlen / tab_st (device, all NULL or none): the rows
+ *     mtblx_get_decompressed takes -- the stored content start, the offset in dst, the length, and
+ *     nonzero where the crate's decompress step returns Err(Io) -- at row j (by_ordinal == 0,
+ *     [n] rows: with sel == NULL on an ascending directory the table as it stands), or at row
+ *     sel[j] (by_ordinal != 0, [ndir] rows: per-ordinal rows for mtblx_table_gather).
+ * The workspace (device, 256-byte aligned, mtblx_stage_workspace_bytes(n); no fill needed) is the
+ * caller's and carries the plan to the emit: same file, directory and selection in both. */
+size_t mtblx_stage_workspace_bytes(uint32_t n);
+int mtblx_stage_plan(const uint8_t* file, uint64_t file_len, const uint64_t* blk_off, const uint32_t* blk_len,
+                     const int32_t* dir_st, const uint8_t* bad, uint32_t ndir, const uint32_t* sel, uint32_t nsel,
+                     uint64_t* totals, void* workspace, size_t ws_bytes, void* stream);
+int mtblx_stage_emit(const uint8_t* file, uint64_t file_len, const uint64_t* blk_off, uint32_t ndir,
+                     const uint32_t* sel, uint32_t nsel, uint8_t* dst, uint64_t dst_cap, uint64_t base, uint64_t total,
+                     uint32_t max_dec_len, uint64_t* dst_off, uint32_t* dec_len, uint64_t* tab_start,
+                     uint64_t* tab_doff, uint64_t* tab_dlen, int32_t* tab_st, int by_ordinal, const void* workspace,
+                     size_t ws_bytes, void* stream);
+
+/* ---- which blocks a batch of queries needs: touch, compaction, the on-demand table ----
+ * mtblx_scan_touch: per query the fresh index seek of Reader::get / ReaderIntoIter::new_from
+ * (src/reader.rs:256-275) on the index block file[index_off .. + index_len), for the start key
+ * keys[key_end[q-1] .. key_end[q]) and the bound keys2[key2_end[q-1] .. key2_end[q]) (empty, or
+ * key2_end == NULL: open ended).  entry_off (device [nent], ascending): the entry offsets of the
+ * index scan chain (mtblx_entry_offsets), entry i <-> directory ordinal i.  lo = the ordinal where
+ * the start key lands, hi = the ordinal where the bound lands plus one (the iterator opens the next
+ * block when a block runs out before the stop rule fires); the bits [lo, min(hi, lo + cap - 1)] are
+ * ORed into want (device u32 [nwords] over the directory, nwords * 32 >= nent; not cleared).  cap:
+ * device [nq], or NULL = cap_all for every query.  Host glue: get k -> (k, k); from k -> (k, none);
+ * range a b -> (a, b); prefix p -> (p, p with its last non-0xff byte incremented and the tail
+ * dropped; none if p is empty or all 0xff).  The result is a HINT: correctness rests on the lookup
+ * kernels, which report a block the table lacks (MTBLX_GET_MISSING / MTBLX_SCAN_FALLBACK).  On a
+ * corrupt index every access stays inside the index block, entry_off and want; a seek that panics,
+ * loops or lands off the chain marks nothing.
+ *
+ * mtblx_bitmap_compact: the set bits of bits & ~exclude (exclude may be NULL) below nbits, ascending,
+ * to list (device [list_cap]; ordinals past list_cap are counted, not written); *count (device).
+ *
+ * mtblx_table_gather: row j of the compact table = (blk_off[o], row_doff[o], row_dlen[o], row_st[o])
+ * for o = list[j] (n rows from per-ordinal arrays of nrow entries).  On a directory whose content
+ * starts ascend with the ordinal (mtblx_dir_ascends: *violations (device) = entries that are not
+ * MTBLX_DIR_OK or whose start is not below the next one's) an ascending list gives the table sorted
+ * by stored start that the lookup kernels binary-search.  All four are asynchronous on `stream`. */
+int mtblx_scan_touch(const uint8_t* file, uint64_t file_len, uint64_t index_off, uint64_t index_len,
+                     const uint64_t* entry_off, uint32_t nent, const uint8_t* keys, const uint64_t* key_end,
+                     const uint8_t* keys2, const uint64_t* key2_end, const uint32_t* cap, uint32_t cap_all, uint32_t nq,
+                     uint32_t* want, uint32_t nwords, void* stream);
+int mtblx_bitmap_compact(const uint32_t* bits, const uint32_t* exclude, uint32_t nbits, uint32_t* list,
+                         uint32_t list_cap, uint32_t* count, void* stream);
+int mtblx_table_gather(const uint32_t* list, uint32_t n, uint32_t nrow, const uint64_t* blk_off,
+                       const uint64_t* row_doff, const uint64_t* row_dlen, const int32_t* row_st, uint64_t* tab_start,
+                       uint64_t* tab_doff, uint64_t* tab_dlen, int32_t* tab_st, void* stream);
+int mtblx_dir_ascends(const uint64_t* blk_off, const int32_t* dir_st, uint32_t ndir, uint32_t* violations,
+                      void* stream);
 
 /* ---- end-to-end decode from host memory (the PCIe-inclusive path of the north star) ----
  * An mtbl file in host memory in (mmap'd or read), the caller's host byte slices out:

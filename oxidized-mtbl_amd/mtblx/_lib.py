@@ -47,6 +47,8 @@ EXPORTS = [
     "mtblx_snappy_compress_workspace_bytes", "mtblx_snappy_slots", "mtblx_snappy_compress_dev", "mtblx_frame_blocks",
     "mtblx_encode_index_c",
     "mtblx_scan_workspace_bytes", "mtblx_scan_plan", "mtblx_scan_emit",
+    "mtblx_stage_workspace_bytes", "mtblx_stage_plan", "mtblx_stage_emit", "mtblx_scan_touch", "mtblx_bitmap_compact",
+    "mtblx_table_gather", "mtblx_dir_ascends",
 ]
 MERGE_MAX_SOURCES, MERGE_MAX_RECORDS = 64, (1 << 32) - 16
 MERGE_GROUPS, MERGE_CONCAT, MERGE_FIRST, MERGE_LAST = range(4)
@@ -314,6 +316,27 @@ def lib() -> C.CDLL:
         L.mtblx_scan_emit.argtypes = _file + [C.c_uint64, C.c_uint64] + _tab + [
             C.c_uint32, C.POINTER(Scanned), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mtblx_scan_emit.restype = C.c_int
+        L.mtblx_stage_workspace_bytes.argtypes = [C.c_uint32]
+        L.mtblx_stage_workspace_bytes.restype = C.c_size_t
+        L.mtblx_stage_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_uint32, u64p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_stage_plan.restype = C.c_int
+        L.mtblx_stage_emit.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]
+        L.mtblx_stage_emit.restype = C.c_int
+        L.mtblx_scan_touch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.mtblx_scan_touch.restype = C.c_int
+        L.mtblx_bitmap_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                           C.c_void_p]
+        L.mtblx_bitmap_compact.restype = C.c_int
+        L.mtblx_table_gather.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 9
+        L.mtblx_table_gather.restype = C.c_int
+        L.mtblx_dir_ascends.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mtblx_dir_ascends.restype = C.c_int
         L.mtblx_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_uint64]
         L.mtblx_host_alloc.restype = C.c_int
         L.mtblx_host_free.argtypes = [C.c_void_p]

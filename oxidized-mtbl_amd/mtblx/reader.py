@@ -21,9 +21,19 @@ Seek-based iteration -- iter_from / iter_prefix / iter_range (src/reader.rs:128-
 stateful ReaderIntoIter with next() / seek() (:219-405) -- goes through the device index seek,
 block_at_index and block seek, decoding only the blocks the iteration reaches (iterator.py).
 get() is the device Reader::get (mtblx_get).
+
+Compressed files: Reader::block's decompress step (src/reader.rs:166-170) runs on the device for
+Snappy (mtblx_stage_plan / mtblx_stage_emit: the stored bytes stay where they are) and on the host
+for Zlib / Zstd (mtblx_decompress_blocks).  get_batch / scan_batch / count_batch on a Snappy file
+decompress only the blocks a batch touches when the index is regular and the directory ascends
+(mtblx_scan_touch -> mtblx_bitmap_compact -> stage -> mtblx_table_gather: the on-demand table, its
+bytes in an arena that grows by doubling), else every block once.  Reader.stage_stats counts both
+sides; ReaderBuilder(snappy_stage="host") keeps the host path (DESIGN.md §4 "Snappy files in the
+Reader").
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 
@@ -124,23 +134,64 @@ class ScanBatch:
         return out
 
 
-class ReaderBuilder:
-    """src/reader.rs:15-30: verify_checksums defaults to true."""
+def prefix_bound(prefix: bytes):
+    """the smallest key above every key that starts with `prefix` (its last non-0xff byte
+    incremented, the tail dropped), or None when there is none (empty or all 0xff): the bound
+    mtblx_scan_touch takes for an iter_prefix query"""
+    p = bytes(prefix).rstrip(b"\xff")
+    if not p:
+        return None
+    return p[:-1] + bytes([p[-1] + 1])
 
-    def __init__(self):
+
+class ReaderBuilder:
+    """src/reader.rs:15-30: verify_checksums defaults to true.  snappy_stage: where the blocks of a
+    Snappy file are decompressed: "device" (mtblx_stage_*, the stored bytes never leave the GPU) or
+    "host" (mtblx_decompress_blocks on CPU threads: the A/B baseline)."""
+
+    def __init__(self, snappy_stage: str = "device"):
         self._verify = True
+        self.snappy_stage(snappy_stage)
 
     def verify_checksums(self, verify: bool) -> "ReaderBuilder":
         self._verify = bool(verify)
         return self
 
+    def snappy_stage(self, where: str) -> "ReaderBuilder":
+        if where not in ("device", "host"):
+            raise ValueError(f"snappy_stage: {where!r} (\"device\" or \"host\")")
+        self._snappy_stage = where
+        return self
+
     def read(self, data, device="cuda") -> "Reader":
-        return Reader(data, self._verify, device)
+        return Reader(data, self._verify, device, snappy_stage=self._snappy_stage)
+
+
+class _OnDemand:
+    """the on-demand table of a Snappy file: which directory entries are resident (bitmap), their
+    per-ordinal rows, the arena their decompressed bytes live in and the compact table built from
+    them"""
+
+    def __init__(self, nent: int, eoffs: torch.Tensor, dev):
+        self.nwords = (nent + 31) // 32
+        self.eoffs = eoffs
+        self.resident = torch.zeros(self.nwords, dtype=torch.int32, device=dev)
+        self.row_start = torch.zeros(nent, dtype=torch.int64, device=dev)
+        self.row_doff = torch.zeros(nent, dtype=torch.int64, device=dev)
+        self.row_dlen = torch.zeros(nent, dtype=torch.int64, device=dev)
+        self.row_st = torch.zeros(nent, dtype=torch.int32, device=dev)
+        self.arena = torch.empty(16, dtype=torch.uint8, device=dev)
+        self.used = 0
+        self.nres = 0
+        z64 = torch.zeros(0, dtype=torch.int64, device=dev)
+        self.table = (z64, z64, z64, torch.zeros(0, dtype=torch.int32, device=dev), 0, self.arena)
 
 
 class Reader:
-    def __init__(self, data, verify_checksums: bool = True, device="cuda"):
+    def __init__(self, data, verify_checksums: bool = True, device="cuda", snappy_stage: str = "device"):
         codec._require_device()
+        if snappy_stage not in ("device", "host"):
+            raise ValueError(f"snappy_stage: {snappy_stage!r} (\"device\" or \"host\")")
         if isinstance(data, torch.Tensor):
             self.file = data.to(device=device, dtype=torch.uint8).contiguous()
             host = None
@@ -169,6 +220,11 @@ class Reader:
         self.meta = list(f.meta)
         self.version = int(f.version)
         self.compression = int(self.meta[2])   # 0..5 (read_footer rejects others: InvalidCompressionAlgorithm)
+        self._snappy_dev = self.compression == 1 and snappy_stage == "device"
+        self._nhost = 0        # blocks decompressed on the host
+        self._ndev = 0         # blocks decompressed on the device
+        self._od = None        # _OnDemand, False = not applicable (full table), None = not decided
+        self._dtab = None
         idx_off = int(self.meta[0])
         if host is None:   # index block bytes to the host (framing + checksum)
             hi = self.len - METADATA_SIZE
@@ -251,6 +307,7 @@ class Reader:
         n[~ok] = 0
         o[~ok] = 0
         nb = o.size
+        self._nhost += int(ok.sum())
         dst = _lib.u8p()
         doff = np.zeros(max(nb, 1), np.uint64)
         dlen = np.zeros(max(nb, 1), np.uint64)
@@ -458,7 +515,19 @@ class Reader:
         """Every data block the directory frames, decompressed on the host (Reader::block's
         decompress step, src/reader.rs:166-170), on the device, with the table
         mtblx_get_decompressed takes: sorted by stored content start."""
-        if getattr(self, "_dtab", None) is None:
+        if self._snappy_dev:
+            od = self._on_demand()
+            if od:
+                return od.table
+            if self._dtab is None:   # the full table, staged on the device
+                off, ln, st = self._framing()
+                buf, _, _, (ts, tdo, tdl, tst), _ = self._stage_all(off, ln, st, None)
+                ok = st == _lib.DIR_OK
+                ts, tdo, tdl, tst = ts[ok], tdo[ok], tdl[ok], tst[ok]
+                order = torch.argsort(ts, stable=True)
+                self._dtab = (ts[order], tdo[order], tdl[order], tst[order], int(order.numel()), buf)
+            return self._dtab
+        if self._dtab is None:
             off, ln, st = self._framing()
             buf, doff, dlen, zerr = self._host_stage(off, ln, st)
             start = off.cpu().numpy().view(np.uint64)
@@ -477,6 +546,7 @@ class Reader:
         them: MTBLX_GET_MISSING) and add them to the table"""
         ts, tdo, tdl, tst, n, dec = self._dec_table()
         L = _lib.lib()
+        self._nhost += len(starts)
         parts, base = [], int(dec.numel())
         s0, o0, l0, z0 = [], [], [], []
         for a, n_ in zip(starts, sizes):
@@ -502,6 +572,172 @@ class Reader:
         extra = torch.from_numpy(np.concatenate(parts) if parts else np.zeros(0, np.uint8)).to(dev)
         self._dtab = (t(start[order]), t(doff[order]), t(dlen[order]), t(zst[order]), int(order.size),
                       torch.cat([dec, extra]))
+
+    # ------------------------------------------------------------------ device staging (Snappy)
+    def _stage_plan(self, off, ln, st, bad, sel, stream=None):
+        """mtblx_stage_plan over a directory (device tensors; sel: int32 ordinals or None)
+        -> (workspace, its size, (layout bytes, largest decompressed length, corrupt preambles))"""
+        L = _lib.lib()
+        ndir = int(off.numel())
+        n = int(sel.numel()) if sel is not None else ndir
+        wsb = int(L.mtblx_stage_workspace_bytes(n))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=self.file.device)   # the caching allocator aligns to 512 bytes
+        totals = (C.c_uint64 * 3)()
+        rc = L.mtblx_stage_plan(C.c_void_p(self.file.data_ptr()), self.len, C.c_void_p(codec._u(off)),
+                                C.c_void_p(codec._u(ln)), C.c_void_p(codec._u(st)),
+                                C.c_void_p(codec._u(bad)) if bad is not None else None, ndir,
+                                C.c_void_p(codec._u(sel)) if sel is not None else None, n if sel is not None else 0,
+                                totals, C.c_void_p(ws.data_ptr()), wsb, C.c_void_p(codec._stream_handle(stream)))
+        if rc != 0:
+            raise RuntimeError(f"mtblx_stage_plan failed: {rc}")
+        return ws, wsb, [int(x) for x in totals]
+
+    def _stage_emit(self, off, sel, ws, wsb, totals, dst, base, doff, dlen, tab, by_ordinal, stream=None):
+        ndir = int(off.numel())
+        n = int(sel.numel()) if sel is not None else ndir
+        p = lambda t: C.c_void_p(codec._u(t)) if t is not None else None   # noqa: E731
+        tab = tab if tab is not None else (None, None, None, None)
+        rc = _lib.lib().mtblx_stage_emit(C.c_void_p(self.file.data_ptr()), self.len, p(off), ndir, p(sel),
+                                         n if sel is not None else 0, C.c_void_p(dst.data_ptr()), int(dst.numel()),
+                                         base, totals[0], min(totals[1], 0xFFFFFFFF), p(doff), p(dlen), p(tab[0]),
+                                         p(tab[1]), p(tab[2]), p(tab[3]), 1 if by_ordinal else 0,
+                                         C.c_void_p(ws.data_ptr()), wsb, C.c_void_p(codec._stream_handle(stream)))
+        if rc != 0:
+            raise RuntimeError(f"mtblx_stage_emit failed: {rc}")
+
+    def _stage_all(self, off, ln, st, bad, stream=None):
+        """Reader::block's decompression step for every entry of a directory, on the device
+        -> (decompressed bytes, offsets int64 [n], lengths int32 [n] (0: failed or skipped),
+        table rows (start, offset, length, Err(Io)) [n], largest length); nothing is read back"""
+        dev = self.file.device
+        n = int(off.numel())
+        ws, wsb, totals = self._stage_plan(off, ln, st, bad, None, stream)
+        buf = torch.empty(max(totals[0], 16), dtype=torch.uint8, device=dev)
+        doff = torch.zeros(n, dtype=torch.int64, device=dev)
+        dlen = torch.zeros(n, dtype=torch.int32, device=dev)
+        tab = (torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int64, device=dev),
+               torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
+        self._stage_emit(off, None, ws, wsb, totals, buf, 0, doff, dlen, tab, False, stream)
+        self._ndev += n
+        return buf, doff, dlen, tab, totals[1]
+
+    def _on_demand(self):
+        """the on-demand table's state, or False where it does not apply: the index must be
+        regular (a seek lands on the scan chain: entry i <-> directory ordinal i) and the stored
+        content starts must ascend with the ordinal (mtblx_dir_ascends, once per Reader)"""
+        if self._od is None:
+            self._od = False
+            eoffs, regular = self._index_chain()
+            if self._snappy_dev and regular and self.nent and eoffs.size == self.nent:
+                dev = self.file.device
+                off, ln, st = self._framing()
+                viol = torch.zeros(1, dtype=torch.int32, device=dev)
+                rc = _lib.lib().mtblx_dir_ascends(C.c_void_p(off.data_ptr()), C.c_void_p(st.data_ptr()), self.nent,
+                                                  C.c_void_p(viol.data_ptr()), C.c_void_p(codec._stream_handle(None)))
+                if rc != 0:
+                    raise RuntimeError(f"mtblx_dir_ascends failed: {rc}")
+                if int(viol.item()) == 0:
+                    self._od = _OnDemand(self.nent, torch.from_numpy(np.ascontiguousarray(eoffs, np.int64)).to(dev), dev)
+        return self._od
+
+    @property
+    def table_mode(self):
+        """how point queries on this compressed file find their blocks: "on-demand" (only the
+        blocks queries touched are decompressed), "full" (every block), None (not compressed)"""
+        if self.compression == 0:
+            return None
+        return "on-demand" if self._snappy_dev and self._on_demand() else "full"
+
+    @property
+    def stage_stats(self):
+        """counters of the decompression step: blocks decompressed on the host and entries handed
+        to the device stage so far (the ones it skips included), blocks resident in the point-query
+        table, and the bytes of its arena (allocated / used)"""
+        od = self._od if self._snappy_dev else None
+        if od:
+            res, arena, used = od.nres, int(od.arena.numel()), od.used
+        elif self._dtab is not None:
+            res, arena = self._dtab[4], int(self._dtab[5].numel())
+            used = arena
+        else:
+            res = arena = used = 0
+        return {"host_blocks": self._nhost, "device_blocks": self._ndev, "resident_blocks": res,
+                "arena_bytes": arena, "arena_used": used}
+
+    def _od_touch(self, kb, ke, k2b, k2e, caps, cap_all, nq, stream=None):
+        """touch -> compact -> stage what is not resident -> rebuild the compact table"""
+        od = self._od
+        if nq == 0:
+            return
+        ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+        with ctx:
+            want = torch.zeros(od.nwords, dtype=torch.int32, device=self.file.device)
+            p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+            rc = _lib.lib().mtblx_scan_touch(C.c_void_p(self.file.data_ptr()), self.len, self.index_off, self.index_len,
+                                             p(od.eoffs), self.nent, p(kb), p(ke), p(k2b), p(k2e), p(caps), cap_all, nq,
+                                             p(want), od.nwords, C.c_void_p(codec._stream_handle(stream)))
+            if rc != 0:
+                raise RuntimeError(f"mtblx_scan_touch failed: {rc}")
+            self._od_stage(want, stream)
+
+    def _od_stage(self, want, stream=None):
+        """stage the entries of the bitmap `want` that are not resident into the arena"""
+        od, dev, L = self._od, self.file.device, _lib.lib()
+        sh = C.c_void_p(codec._stream_handle(stream))
+        lst = torch.empty(self.nent, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+        rc = L.mtblx_bitmap_compact(C.c_void_p(want.data_ptr()), C.c_void_p(od.resident.data_ptr()), self.nent,
+                                    C.c_void_p(lst.data_ptr()), self.nent, C.c_void_p(cnt.data_ptr()), sh)
+        if rc != 0:
+            raise RuntimeError(f"mtblx_bitmap_compact failed: {rc}")
+        n = int(cnt.item())
+        if n == 0:
+            return
+        sel = lst[:n]
+        off, ln, st = self._framing()
+        ws, wsb, totals = self._stage_plan(off, ln, st, None, sel, stream)
+        need = od.used + totals[0]
+        if need > od.arena.numel():       # grows by doubling; offsets are relative to the base
+            grown = torch.empty(max(2 * int(od.arena.numel()), need), dtype=torch.uint8, device=dev)
+            grown[: od.used] = od.arena[: od.used]
+            od.arena = grown
+        self._stage_emit(off, sel, ws, wsb, totals, od.arena, od.used, None, None,
+                         (od.row_start, od.row_doff, od.row_dlen, od.row_st), True, stream)
+        od.used = need
+        od.resident |= want
+        self._ndev += n
+        rc = L.mtblx_bitmap_compact(C.c_void_p(od.resident.data_ptr()), None, self.nent, C.c_void_p(lst.data_ptr()),
+                                    self.nent, C.c_void_p(cnt.data_ptr()), sh)
+        if rc != 0:
+            raise RuntimeError(f"mtblx_bitmap_compact failed: {rc}")
+        od.nres = m = int(cnt.item())
+        ts = torch.empty(m, dtype=torch.int64, device=dev)
+        tdo = torch.empty(m, dtype=torch.int64, device=dev)
+        tdl = torch.empty(m, dtype=torch.int64, device=dev)
+        tst = torch.empty(m, dtype=torch.int32, device=dev)
+        rc = L.mtblx_table_gather(C.c_void_p(lst.data_ptr()), m, self.nent, C.c_void_p(off.data_ptr()),
+                                  C.c_void_p(od.row_doff.data_ptr()), C.c_void_p(od.row_dlen.data_ptr()),
+                                  C.c_void_p(od.row_st.data_ptr()), C.c_void_p(ts.data_ptr()),
+                                  C.c_void_p(tdo.data_ptr()), C.c_void_p(tdl.data_ptr()), C.c_void_p(tst.data_ptr()), sh)
+        if rc != 0:
+            raise RuntimeError(f"mtblx_table_gather failed: {rc}")
+        od.table = (ts, tdo, tdl, tst, m, od.arena)
+
+    def _od_missing(self, starts, stream=None) -> bool:
+        """a lookup reached stored blocks the on-demand table lacks (the touch is a hint): stage
+        those that are directory entries; False when one is not (the caller builds the full table)"""
+        od = self._od
+        if getattr(self, "_starts_host", None) is None:
+            self._starts_host = self._framing()[0].cpu().numpy()
+        pos = np.searchsorted(self._starts_host, np.asarray(starts, np.int64))
+        if (pos >= self.nent).any() or (self._starts_host[np.minimum(pos, self.nent - 1)] != starts).any():
+            return False
+        bits = np.zeros(od.nwords, np.uint32)
+        np.bitwise_or.at(bits, pos >> 5, (np.uint32(1) << (pos & 31).astype(np.uint32)))
+        ctx = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+        with ctx:
+            self._od_stage(torch.from_numpy(bits.view(np.int32)).to(self.file.device), stream)
+        return True
 
     @property
     def value_source(self):
@@ -535,6 +771,9 @@ class Reader:
             # a lookup that reaches a stored block the table lacks (MTBLX_GET_MISSING: only a
             # corrupt index read with verification off leads there) gets that block decompressed
             # and added, and the batch runs again; every round adds a block, so this ends
+            if self._snappy_dev and self._on_demand():
+                # Reader::get opens the block its key lands in and, when the seek runs past it, the next
+                self._od_touch(kb, ke, kb, ke, None, 2, nq, stream)
             for _ in range(1 + 4096):
                 ts, tdo, tdl, tst, ntab, dec = self._dec_table()
                 rc = _lib.lib().mtblx_get_decompressed(
@@ -549,6 +788,10 @@ class Reader:
                 if not miss.any():
                     break
                 pairs = sorted(set(zip(vo[:nq].cpu().numpy()[miss].tolist(), vl[:nq].cpu().numpy()[miss].tolist())))
+                if self._snappy_dev and self._od:
+                    if not self._od_missing([a for a, _ in pairs], stream):
+                        self._od = False   # a block outside the directory: the full table, then the host path
+                    continue
                 self._dtab_add([a for a, _ in pairs], [b for _, b in pairs])
             else:
                 raise RuntimeError("get_batch: missing blocks did not converge")
@@ -655,6 +898,14 @@ class Reader:
             tab = (None, None, None, None, 0, None)
             keep = None
         else:
+            if self._snappy_dev and nq and self._on_demand():
+                # the bound of each query (mtblx.h, mtblx_scan_touch); Reader::get opens at most two blocks
+                bounds = [k if t == _lib.SCAN_GET else k2 if t == _lib.SCAN_RANGE else
+                          (prefix_bound(k) or b"") if t == _lib.SCAN_PREFIX else b"" for t, k, k2 in qs]
+                bb, be = blob(bounds)
+                caps = torch.from_numpy(np.array([min(max_blocks, 2) if t == _lib.SCAN_GET else max_blocks
+                                                  for t, _, _ in qs], dtype=np.uint32).view(np.int32)).to(dev)
+                self._od_touch(kb, ke, bb, be, caps, 0, nq, stream)
             keep = self._dec_table()
             ts, tdo, tdl, tst, ntab, dec = keep
             tab = (C.c_void_p(ts.data_ptr()), C.c_void_p(tdo.data_ptr()), C.c_void_p(tdl.data_ptr()),
@@ -861,7 +1112,17 @@ class Reader:
         return self._decompressed(int(s.data_off), int(s.data_len))
 
     def _decompressed(self, off: int, n: int):
-        """src/compression.rs:57-68 on the host for one stored block -> content on the device"""
+        """src/compression.rs:57-68 for one stored block -> content on the device (Snappy: on the
+        device; the other codecs and a stored content >= 4 GiB: on the host)"""
+        if self._snappy_dev and n <= 0xFFFFFFFF:
+            dev = self.file.device
+            o = torch.tensor([off], dtype=torch.int64, device=dev)
+            ln = torch.from_numpy(np.array([n], np.uint32).view(np.int32)).to(dev)
+            buf, doff, dlen, tab, _ = self._stage_all(o, ln, torch.zeros(1, dtype=torch.int32, device=dev), None)
+            if int(tab[3][0].item()):
+                raise MtblError(7)
+            return buf, int(doff[0].item()), int(dlen[0].item()) & 0xFFFFFFFF
+        self._nhost += 1
         raw = self.file[off: off + n].cpu().numpy()
         L = _lib.lib()
         out = _lib.u8p()
@@ -893,8 +1154,17 @@ class Reader:
                 okl = torch.where(st == _lib.DIR_OK, ln, torch.zeros_like(ln))
                 batch = codec.DeviceBatch(self.file, off, okl, int(okl.max().item()))
                 bad = codec.crc32c_blocks(batch, framed=True)[1]
+        bad_dev = bad
         bad = bad.cpu().numpy() if bad is not None else np.zeros(n, np.uint8)
-        if self.compression != 0:
+        if self._snappy_dev:
+            # the stored bytes stay where they are; a preamble is a u32, so no content here is >= 4 GiB
+            buf, doff, dlen, tab, mx = self._stage_all(off, ln, st, bad_dev)
+            zerr = tab[3].cpu().numpy()
+            uoff = doff.cpu().numpy()
+            uln = dlen.cpu().numpy().view(np.uint32).astype(np.int64)
+            batch = codec.DeviceBatch(buf, doff, dlen, int(uln.max()) if n else 0)
+            where = (buf, uoff, uln)
+        elif self.compression != 0:
             buf, uoff, uln, zerr = self._host_stage(off, ln, st)
             small = np.where(uln > 0xFFFFFFFF, 0, uln).astype(np.uint32)   # >= 4 GiB: _big_content
             batch = codec.DeviceBatch.from_host(buf, uoff, small, device=self.file.device)
