@@ -1297,11 +1297,23 @@ inline std::vector<Reader::Records> Reader::scan_batch(const std::vector<ScanQue
 // sources were added; the empty-key quirk of :182-186 is kept; an out-of-order source throws
 // UnsortedSource (the reference does not check).  More than MTBLX_MERGE_MAX_SOURCES sources are
 // merged in rounds with the same mode; a merge function is called once, at the end, and never
-// for a group of one (:200-207).
+// for a group of one (:200-207).  A MergeReduce (u64 sum / min / max per 8-byte field, mtblx.h
+// "Device merge functions") is evaluated on the device (mtblx_merge_emit_reduce), per round: the
+// ops are associative and commutative and a group of one passes through, so the rounds give the
+// bytes of one application; a group of two or more with a value of another length throws MergeError.
 struct MergeConcat {};   // the group's values joined in source order (the reference's test merge function)
 struct MergeFirst {};    // the first-added source's value
 struct MergeLast {};     // the last-added source's value
 using MergeFn = std::function<Bytes(const Bytes& key, const std::vector<Bytes>& values)>;
+struct MergeReduce {     // one op (MTBLX_REDUCE_SUM / _MIN / _MAX) per little-endian u64 field, 1 to 8 of them
+  std::vector<int> ops;
+  static MergeReduce sum() { return MergeReduce{{MTBLX_REDUCE_SUM}}; }
+  static MergeReduce min() { return MergeReduce{{MTBLX_REDUCE_MIN}}; }
+  static MergeReduce max() { return MergeReduce{{MTBLX_REDUCE_MAX}}; }
+};
+struct MergeError : std::runtime_error {   // the reference's Error::Merge
+  MergeError() : std::runtime_error("merge: a group of two or more holds a value of another length than 8 * nfields") {}
+};
 struct UnsortedSource : std::runtime_error {
   UnsortedSource() : std::runtime_error("merge source out of order") {}
 };
@@ -1311,8 +1323,21 @@ struct HostGroups {   // mtblx_merged on the host; ge is empty in the single-val
   Bytes keys, vals;
   std::vector<uint64_t> ke, ve, ge;
 };
-// one plan + emit over sources [i0, i1) (at most MTBLX_MERGE_MAX_SOURCES)
-inline HostGroups merge_once(const std::vector<HostGroups>& src, size_t i0, size_t i1, int mode) {
+// a MergeReduce as the C ABI takes it; refused here, before any device work, if it is not a spec
+inline mtblx_reduce reduce_spec(const MergeReduce& r) {
+  if (r.ops.empty() || r.ops.size() > MTBLX_REDUCE_MAX_FIELDS) throw std::invalid_argument("MergeReduce: 1 to 8 ops");
+  mtblx_reduce spec{};
+  spec.nfields = static_cast<uint32_t>(r.ops.size());
+  for (size_t f = 0; f < r.ops.size(); ++f) {
+    if (r.ops[f] < MTBLX_REDUCE_SUM || r.ops[f] > MTBLX_REDUCE_MAX) throw std::invalid_argument("MergeReduce: unknown op");
+    spec.op[f] = static_cast<uint8_t>(r.ops[f]);
+  }
+  return spec;
+}
+// one plan + emit over sources [i0, i1) (at most MTBLX_MERGE_MAX_SOURCES); with a reduce spec the
+// emit is mtblx_merge_emit_reduce and `mode` is MTBLX_MERGE_FIRST, whose layout it has
+inline HostGroups merge_once(const std::vector<HostGroups>& src, size_t i0, size_t i1, int mode,
+                             const mtblx_reduce* rd = nullptr) {
   const uint32_t ns = static_cast<uint32_t>(i1 - i0);
   std::vector<DevBuf> bufs;
   std::vector<mtblx_records> recs(ns ? ns : 1);
@@ -1340,9 +1365,12 @@ inline HostGroups merge_once(const std::vector<HostGroups>& src, size_t i0, size
   DevBuf k(tot[1]), ke(8 * tot[0]), v(tot[3]), ve(8 * nve), ge(8 * nge), fl(4);
   const mtblx_merged out{k.as<uint8_t>(),  tot[1],  ke.as<uint64_t>(), 8 * tot[0], v.as<uint8_t>(), tot[3],
                          ve.as<uint64_t>(), 8 * nve, ge.as<uint64_t>(), 8 * nge,    fl.as<uint32_t>()};
-  abi_check(mtblx_merge_emit(recs.data(), ns, mode, &out, ws.p, wsb, nullptr), "mtblx_merge_emit");
+  if (rd) abi_check(mtblx_merge_emit_reduce(recs.data(), ns, rd, &out, ws.p, wsb, nullptr), "mtblx_merge_emit_reduce");
+  else abi_check(mtblx_merge_emit(recs.data(), ns, mode, &out, ws.p, wsb, nullptr), "mtblx_merge_emit");
   hip_check(hipDeviceSynchronize(), "sync");
-  if (download<uint32_t>(fl.p, 1)[0]) throw std::runtime_error("mtblx_merge_emit: flags set");
+  const uint32_t flags = download<uint32_t>(fl.p, 1)[0];
+  if (flags & MTBLX_MERGE_BADVALUE) throw MergeError();
+  if (flags) throw std::runtime_error("mtblx_merge_emit: flags set");
   HostGroups r;
   r.ke = download<uint64_t>(ke.p, tot[0]);
   r.ve = download<uint64_t>(ve.p, nve);
@@ -1386,13 +1414,13 @@ inline HostGroups regroup(const std::vector<HostGroups>& parts, size_t i0, size_
   for (uint64_t e : vb.ve) r.ge.push_back(e / 8);
   return r;
 }
-inline HostGroups merge_all(std::vector<HostGroups> src, int mode) {
+inline HostGroups merge_all(std::vector<HostGroups> src, int mode, const mtblx_reduce* rd = nullptr) {
   bool first = true;
   while (first || src.size() > 1) {
     std::vector<HostGroups> next;
     for (size_t i = 0; i < src.size() || (first && src.empty() && next.empty()); i += MTBLX_MERGE_MAX_SOURCES) {
       const size_t e = std::min(src.size(), i + MTBLX_MERGE_MAX_SOURCES);
-      next.push_back(mode == MTBLX_MERGE_GROUPS && !first ? regroup(src, i, e) : merge_once(src, i, e, mode));
+      next.push_back(mode == MTBLX_MERGE_GROUPS && !first ? regroup(src, i, e) : merge_once(src, i, e, mode, rd));
     }
     src = std::move(next);
     first = false;
@@ -1411,6 +1439,7 @@ class MergerBuilder {   // src/merger.rs:66-94
   explicit MergerBuilder(MergeConcat) : mode_(MTBLX_MERGE_CONCAT) {}
   explicit MergerBuilder(MergeFirst) : mode_(MTBLX_MERGE_FIRST) {}
   explicit MergerBuilder(MergeLast) : mode_(MTBLX_MERGE_LAST) {}
+  explicit MergerBuilder(const MergeReduce& r) : mode_(MTBLX_MERGE_FIRST), rd_(detail::reduce_spec(r)), reduce_(true) {}
   MergerBuilder& add(Reader source) { push(std::move(source)); return *this; }
   void push(Reader source) { sources_.push_back(std::move(source)); }
   MergerBuilder& extend(std::vector<Reader> sources) {
@@ -1422,6 +1451,8 @@ class MergerBuilder {   // src/merger.rs:66-94
  private:
   int mode_;
   MergeFn fn_;
+  mtblx_reduce rd_{};   // used when reduce_: mode_ is then MTBLX_MERGE_FIRST, the layout of the result
+  bool reduce_ = false;
   std::vector<Reader> sources_;
 };
 
@@ -1460,7 +1491,8 @@ class Merger {
 
  private:
   friend class MergerBuilder;
-  Merger(int mode, MergeFn fn, std::vector<Reader> s) : mode_(mode), fn_(std::move(fn)), sources_(std::move(s)) {}
+  Merger(int mode, MergeFn fn, std::vector<Reader> s, const mtblx_reduce& rd, bool reduce)
+      : mode_(mode), fn_(std::move(fn)), rd_(rd), reduce_(reduce), sources_(std::move(s)) {}
   detail::HostGroups run(int mode) const {
     std::vector<detail::HostGroups> src(sources_.size());
     for (size_t i = 0; i < sources_.size(); ++i) {
@@ -1473,13 +1505,15 @@ class Merger {
         s.ve.push_back(s.vals.size());
       }
     }
-    return detail::merge_all(std::move(src), mode);
+    return detail::merge_all(std::move(src), mode, reduce_ && mode != MTBLX_MERGE_GROUPS ? &rd_ : nullptr);
   }
   int mode_;
   MergeFn fn_;
+  mtblx_reduce rd_;
+  bool reduce_;
   std::vector<Reader> sources_;
 };
-inline Merger MergerBuilder::build() { return Merger(mode_, std::move(fn_), std::move(sources_)); }
+inline Merger MergerBuilder::build() { return Merger(mode_, std::move(fn_), std::move(sources_), rd_, reduce_); }
 
 // ------------------------------------------------------------------ Sorter (src/sorter.rs)
 // SorterBuilder / Sorter (src/sorter.rs:25-258) over the device sort (mtblx_sort_plan /
@@ -1490,14 +1524,17 @@ inline Merger MergerBuilder::build() { return Merger(mode_, std::move(fn_), std:
 // host memory between the device calls, not in compressed temp files: chunk_compression_type /
 // _level are accepted and stored and have no effect.  Promised on top of the reference (mtblx.h):
 // the values of a key are in insertion order (the reference sorts with sort_unstable_by).  A merge
-// function is never called for a group of one (:166-170).
+// function is never called for a group of one (:166-170).  A MergeReduce is evaluated on the device
+// per chunk (mtblx_sort_emit_reduce) and again over the chunks (mtblx_merge_emit_reduce), as the
+// reference applies its merge function; the bytes are those of one application (mtblx.h).
 constexpr size_t DEFAULT_NB_CHUNKS = 25, MIN_NB_CHUNKS = 1;                              // src/lib.rs:11-12
 constexpr size_t DEFAULT_SORTER_MEMORY = 1073741824, MIN_SORTER_MEMORY = 10485760;       // :13-14
 constexpr size_t INITIAL_SORTER_VEC_SIZE = 131072;                                       // :15
 
 namespace detail {
-// one mtblx_sort_plan + mtblx_sort_emit over one batch of records in any order
-inline HostGroups sort_once(const HostGroups& s, int mode) {
+// one mtblx_sort_plan + mtblx_sort_emit (with a reduce spec: mtblx_sort_emit_reduce, mode
+// MTBLX_MERGE_FIRST) over one batch of records in any order
+inline HostGroups sort_once(const HostGroups& s, int mode, const mtblx_reduce* rd = nullptr) {
   const DevBuf dk = upload(s.keys.data(), s.keys.size()), dke = upload(s.ke.data(), s.ke.size()),
                dv = upload(s.vals.data(), s.vals.size()), dve = upload(s.ve.data(), s.ve.size());
   const mtblx_records rec{dk.as<uint8_t>(), dke.as<uint64_t>(), dv.as<uint8_t>(), dve.as<uint64_t>(), s.ke.size()};
@@ -1511,9 +1548,12 @@ inline HostGroups sort_once(const HostGroups& s, int mode) {
   DevBuf k(tot[1]), ke(8 * tot[0]), v(tot[3]), ve(8 * nve), ge(8 * nge), fl(4);
   const mtblx_merged out{k.as<uint8_t>(),  tot[1],  ke.as<uint64_t>(), 8 * tot[0], v.as<uint8_t>(), tot[3],
                          ve.as<uint64_t>(), 8 * nve, ge.as<uint64_t>(), 8 * nge,    fl.as<uint32_t>()};
-  abi_check(mtblx_sort_emit(&rec, mode, &out, ws.p, wsb, nullptr), "mtblx_sort_emit");
+  if (rd) abi_check(mtblx_sort_emit_reduce(&rec, rd, &out, ws.p, wsb, nullptr), "mtblx_sort_emit_reduce");
+  else abi_check(mtblx_sort_emit(&rec, mode, &out, ws.p, wsb, nullptr), "mtblx_sort_emit");
   hip_check(hipDeviceSynchronize(), "sync");
-  if (download<uint32_t>(fl.p, 1)[0]) throw std::runtime_error("mtblx_sort_emit: flags set");
+  const uint32_t flags = download<uint32_t>(fl.p, 1)[0];
+  if (flags & MTBLX_MERGE_BADVALUE) throw MergeError();
+  if (flags) throw std::runtime_error("mtblx_sort_emit: flags set");
   HostGroups r;
   r.ke = download<uint64_t>(ke.p, tot[0]);
   r.ve = download<uint64_t>(ve.p, nve);
@@ -1546,6 +1586,7 @@ class SorterBuilder {   // src/sorter.rs:17-70
   explicit SorterBuilder(MergeConcat) : mode_(MTBLX_MERGE_CONCAT) {}
   explicit SorterBuilder(MergeFirst) : mode_(MTBLX_MERGE_FIRST) {}
   explicit SorterBuilder(MergeLast) : mode_(MTBLX_MERGE_LAST) {}
+  explicit SorterBuilder(const MergeReduce& r) : mode_(MTBLX_MERGE_FIRST), rd_(detail::reduce_spec(r)), reduce_(true) {}
   SorterBuilder& max_memory(size_t memory) { max_memory_ = std::max(memory, MIN_SORTER_MEMORY); return *this; }         // :37
   SorterBuilder& max_nb_chunks(size_t nb_chunks) { max_nb_chunks_ = std::max(nb_chunks, MIN_NB_CHUNKS); return *this; }  // :44
   SorterBuilder& chunk_compression_type(CompressionType c) { ctype_ = c; return *this; }   // stored, no effect
@@ -1555,6 +1596,8 @@ class SorterBuilder {   // src/sorter.rs:17-70
  private:
   int mode_;
   MergeFn fn_;
+  mtblx_reduce rd_{};   // used when reduce_: mode_ is then MTBLX_MERGE_FIRST, the layout of the result
+  bool reduce_ = false;
   size_t max_memory_ = DEFAULT_SORTER_MEMORY, max_nb_chunks_ = DEFAULT_NB_CHUNKS;   // :28-29
   CompressionType ctype_ = CompressionType::Snappy;                                  // :30
   uint32_t clevel_ = 0;                                                              // :31
@@ -1605,19 +1648,20 @@ class Sorter {
 
  private:
   friend class SorterBuilder;
-  Sorter(int mode, MergeFn fn, size_t max_memory, size_t max_nb_chunks)
-      : mode_(mode), fn_(std::move(fn)), max_memory_(max_memory), max_nb_chunks_(max_nb_chunks) {}
+  Sorter(int mode, MergeFn fn, const mtblx_reduce& rd, bool reduce, size_t max_memory, size_t max_nb_chunks)
+      : mode_(mode), fn_(std::move(fn)), rd_(rd), reduce_(reduce), max_memory_(max_memory), max_nb_chunks_(max_nb_chunks) {}
+  const mtblx_reduce* rd() const { return reduce_ ? &rd_ : nullptr; }
   void write_chunk() {                                                 // :142-197
     chunk_sizes_.push_back(pending_.ke.size());
     chunks_.push_back(mode_ == MTBLX_MERGE_GROUPS ? detail::apply_fn(detail::sort_once(pending_, mode_), fn_)
-                                                  : detail::sort_once(pending_, mode_));
+                                                  : detail::sort_once(pending_, mode_, rd()));
     pending_ = detail::HostGroups();
     entry_bytes_ = 0;                                                  // :192
     len_ = 0;                                                          // :155 drain(..): the capacity stays
   }
   detail::HostGroups merged() const {   // a Merger over the chunks, oldest first
     return mode_ == MTBLX_MERGE_GROUPS ? detail::apply_fn(detail::merge_all(chunks_, mode_), fn_)
-                                       : detail::merge_all(chunks_, mode_);
+                                       : detail::merge_all(chunks_, mode_, rd());
   }
   void merge_chunks() {                                                // :199-233: the result is the only, hence oldest, chunk
     detail::HostGroups m = merged();
@@ -1627,13 +1671,15 @@ class Sorter {
   }
   int mode_;
   MergeFn fn_;
+  mtblx_reduce rd_;
+  bool reduce_;
   size_t max_memory_, max_nb_chunks_;
   std::vector<detail::HostGroups> chunks_;
   detail::HostGroups pending_;
   size_t entry_bytes_ = 0, len_ = 0, capacity_ = INITIAL_SORTER_VEC_SIZE, merges_ = 0;
   std::vector<size_t> chunk_sizes_;
 };
-inline Sorter SorterBuilder::build() { return Sorter(mode_, std::move(fn_), max_memory_, max_nb_chunks_); }
+inline Sorter SorterBuilder::build() { return Sorter(mode_, std::move(fn_), rd_, reduce_, max_memory_, max_nb_chunks_); }
 template <class F>
 inline Sorter::Sorter(F merge) : Sorter(SorterBuilder(std::move(merge)).build()) {}
 

@@ -38,8 +38,8 @@ extern "C" {
 
 #define MTBLX_ABI_VERSION 3   /* 3: the block cut takes a caller-owned workspace (round 6).  Still 3 with
                                  mtblx_decode_blocks_valpos / mtblx_pipe_decode_valpos and with the
-                                 mtblx_merge_*, mtblx_sort_*, mtblx_scan_* and mtblx_stage_* calls: added symbols,
-                                 no existing one changed */
+                                 mtblx_merge_*, mtblx_sort_*, mtblx_scan_* and mtblx_stage_* calls (the two
+                                 mtblx_*_emit_reduce among them): added symbols, no existing one changed */
 
 /* ---- API return codes ---- */
 #define MTBLX_OK 0
@@ -695,6 +695,50 @@ int mtblx_sort_emit(const mtblx_records* in, int mode, const mtblx_merged* out, 
  * [2 .. passes + 1] the merge passes, [passes + 2] the grouping.  phase_cap >= passes + 3. */
 int mtblx_sort_plan_timed(const mtblx_records* in, uint64_t* totals, void* workspace, size_t ws_bytes, void* stream,
                           float* phase_ms, uint32_t phase_cap);
+
+/* ---- Device merge functions: u64 sum / min / max for the Merger and the Sorter ----
+ * The reference's merge function is Fn(&[u8], &[Vec<u8>]) -> Result<Vec<u8>, U> (src/merger.rs:145-147,
+ * src/sorter.rs:117-118); the three single-value modes above only join or pick values.  A reduce
+ * spec is a merge function that adds, evaluated on the device: 1 to MTBLX_REDUCE_MAX_FIELDS fields,
+ * each an unsigned 64-bit little-endian integer with one op, MTBLX_REDUCE_SUM (wrapping, mod 2^64),
+ * _MIN or _MAX (unsigned).  W = 8 * nfields is the value width.  Per group, after the empty-key
+ * quirk has dropped what it drops (the merge only, as in every mode):
+ *  - a group of one value comes out unchanged, whatever its length: the reference never calls the
+ *    merge function for it (src/merger.rs:200-201, src/sorter.rs:166-167);
+ *  - a group of two or more whose values are all exactly W bytes long gives one W-byte value,
+ *    field f reduced with op[f] over the group;
+ *  - a group of two or more with a value of any other length is the reference's Err from the merge
+ *    function (Error::Merge): MTBLX_MERGE_BADVALUE is set in *flags, that group's value bytes are
+ *    unspecified but inside its slot, and nothing is written outside the layout.
+ * The three ops are associative and commutative and a group of one passes through, so applying the
+ * spec per round of MTBLX_MERGE_MAX_SOURCES sources, per Sorter chunk and again when the chunks are
+ * merged gives the same bytes as one application over all values of a key (the reference's Sorter
+ * applies its merge function that way too), and an erroneous input stays erroneous: a value of
+ * another length survives every round unchanged until it meets a partner.
+ * The output layout is exactly MTBLX_MERGE_FIRST's: in every valid group the output is as long as
+ * the group's first value (its own length for a group of one, W otherwise), so totals[] of the
+ * plan, the capacities (totals[3] bounds vals; the bytes used are val_end[groups - 1]) and the
+ * workspace are those of an emit in MTBLX_MERGE_FIRST mode, and out->grp_end is unused.  Both calls
+ * are asynchronous like the emits they sit beside and take the workspace of a successful
+ * mtblx_merge_plan / mtblx_sort_plan over the same records; it is written (a per-tile array for
+ * the groups that cross a tile of 1024 merged records), hence not const.  MTBLX_MERGE_OVERFLOW and
+ * MTBLX_MERGE_NOT_PLANNED as in the plain emits.  MTBLX_E_INVAL, before any device work: a NULL spec,
+ * nfields 0 or above MTBLX_REDUCE_MAX_FIELDS, an op above MTBLX_REDUCE_MAX, and everything the plain
+ * emits refuse. */
+#define MTBLX_REDUCE_SUM 0
+#define MTBLX_REDUCE_MIN 1
+#define MTBLX_REDUCE_MAX 2
+#define MTBLX_REDUCE_MAX_FIELDS 8
+#define MTBLX_MERGE_BADVALUE 4u     /* *flags of the two calls below: a group of two or more holds a
+                                       value that is not 8 * nfields bytes long                         */
+typedef struct mtblx_reduce {
+  uint32_t nfields;
+  uint8_t op[MTBLX_REDUCE_MAX_FIELDS];
+} mtblx_reduce;
+int mtblx_merge_emit_reduce(const mtblx_records* src, uint32_t nsrc, const mtblx_reduce* spec,
+                            const mtblx_merged* out, void* workspace, size_t ws_bytes, void* stream);
+int mtblx_sort_emit_reduce(const mtblx_records* in, const mtblx_reduce* spec, const mtblx_merged* out,
+                           void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- snappy raw decompression on the device (f4) ----
  * Reader::block's decompression step for CompressionType::Snappy (src/reader.rs:166-170 ->

@@ -46,6 +46,7 @@ constexpr uint64_t kSortMagic = 0x5354424c58535254ull;
 
 // workspace header words (u64)
 enum { H_GROUPS = 0, H_KEYB, H_NVAL, H_VALB, H_DROPPED, H_FLAGS, H_SKIP, H_PLANNED, H_FIRSTB, H_LASTB, H_WORDS = 32 };
+constexpr int kReduceEdgeWords = 18;   // u64 words per tile of the device merge functions' edge array (reduce_dev.h)
 constexpr int kChan = 6;   // groups, key bytes, values, value bytes, first-value bytes, last-value bytes
 
 struct alignas(16) Handle {
@@ -502,7 +503,7 @@ __global__ void __launch_bounds__(kThreads) k_merge_emit(SrcTab t, const uint64_
 
 // ---- host side ----
 struct Layout {
-  size_t hdr, h0, h1, flag, gi, vi, koff, voff, foff, loff, tiles, total;
+  size_t hdr, h0, h1, flag, gi, vi, koff, voff, foff, loff, tiles, edges, total;
   uint32_t ntiles;
 };
 
@@ -523,6 +524,7 @@ Layout layout(uint64_t n) {
   L.foff = p; p += up256(8 * n);
   L.loff = p; p += up256(8 * n);
   L.tiles = p; p += up256(8ull * kChan * L.ntiles);
+  L.edges = p; p += up256(8ull * kReduceEdgeWords * L.ntiles);   // the reducers' per-tile edge records (reduce_dev.h)
   L.total = p;
   return L;
 }

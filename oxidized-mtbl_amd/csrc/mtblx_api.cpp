@@ -199,6 +199,41 @@ extern "C" int mtblx_sort_emit(const mtblx_records* in, int mode, const mtblx_me
   return mtblx_sort_impl_emit(in, mode, out, ws, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- device merge functions (csrc/reduce_dev.h): the spec is checked before any HIP call ----
+extern "C" int mtblx_merge_impl_emit_reduce(const mtblx_records* src, uint32_t nsrc, const mtblx_reduce* spec,
+                                            const mtblx_merged* out, void* ws, hipStream_t s);
+extern "C" int mtblx_sort_impl_emit_reduce(const mtblx_records* in, const mtblx_reduce* spec, const mtblx_merged* out,
+                                           void* ws, hipStream_t s);
+
+static int reduce_check(const mtblx_reduce* spec, const mtblx_merged* out) {
+  if (!spec || spec->nfields < 1 || spec->nfields > MTBLX_REDUCE_MAX_FIELDS) return MTBLX_E_INVAL;
+  for (uint32_t f = 0; f < spec->nfields; ++f)
+    if (spec->op[f] > MTBLX_REDUCE_MAX) return MTBLX_E_INVAL;
+  if (!out || !out->flags) return MTBLX_E_INVAL;
+  if ((!out->keys && out->keys_cap) || (!out->key_end && out->key_end_cap) || (!out->vals && out->vals_cap) ||
+      (!out->val_end && out->val_end_cap))
+    return MTBLX_E_INVAL;
+  return MTBLX_OK;
+}
+
+extern "C" int mtblx_merge_emit_reduce(const mtblx_records* src, uint32_t nsrc, const mtblx_reduce* spec,
+                                       const mtblx_merged* out, void* ws, size_t wsb, void* stream) {
+  int c = reduce_check(spec, out);
+  if (c != MTBLX_OK) return c;
+  c = merge_check(src, nsrc, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_merge_impl_emit_reduce(src, nsrc, spec, out, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mtblx_sort_emit_reduce(const mtblx_records* in, const mtblx_reduce* spec, const mtblx_merged* out,
+                                      void* ws, size_t wsb, void* stream) {
+  int c = reduce_check(spec, out);
+  if (c != MTBLX_OK) return c;
+  c = sort_check(in, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_sort_impl_emit_reduce(in, spec, out, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
 // ---- batched scans (csrc/scan.hip): the argument checks need no device ----
 extern "C" size_t mtblx_scan_impl_ws_bytes(uint32_t nq);
 extern "C" int mtblx_scan_impl_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,

@@ -1,0 +1,315 @@
+// reduce_dev.h — the device merge functions of the Merger (merge.hip) and the Sorter (sort.hip):
+// a reduce spec of 1 to 8 unsigned 64-bit little-endian fields, each summed (mod 2^64), min-ed or
+// max-ed over the values of a group (include/mtblx.h "Device merge functions").
+//
+// The output has MTBLX_MERGE_FIRST's layout, so the emit is k_merge_emit in FIRST mode (keys,
+// key_end, every group's first value at foff, val_end: a group of one is finished by it) followed
+// by a segmented reduction over the merged handle order that overwrites the W = 8 * F bytes of
+// every group of two or more:
+//   k_reduce_tile   a workgroup owns kTile consecutive merged records, kPer per thread.  A record
+//                   of a group of two or more (not both head and tail) brings its F fields, or,
+//                   where its value is not W bytes long, the "bad" bit and MTBLX_MERGE_BADVALUE.  An
+//                   inclusive segmented scan keyed on the head flags (thread-serial over kPer
+//                   records, __shfl_up inside the wave, LDS across the four waves) leaves the
+//                   group's result with its tail; a tail whose head lies in the same tile stores it
+//                   at the group's slot.  What crosses the tile's edges goes to the tile's edge
+//                   record: the lead partial (the records before the first head; the whole tile if
+//                   it has none), the trail partial (from the last head to the tile's end), whether
+//                   the tile has a head, whether the trail's group goes on, the trail's head index
+//   k_reduce_edges  a wave per tile whose trailing group goes on: its trail combined with the lead
+//                   partials of the following tiles up to and including the first with a head (or
+//                   the last tile), 64 tiles per step, stored at the head's slot
+// The slot of a group of two or more whose values are all W bytes long is [foff[i] - W, foff[i])
+// for every record i of it but the head (foff counts first-value bytes of the groups up to and
+// including i's once i is past the head).  A group with a bad value is not stored at all: its slot
+// keeps the first value k_merge_emit put there, so nothing is written outside a slot.
+// No workgroup waits for another: the launches are ordered by the stream.  The ops are
+// associative and commutative and the results exact, so no result depends on evaluation order; the
+// output slots are unaligned and written with plain (packed) stores, never with atomics.
+#pragma once
+#include "merge_dev.h"
+
+namespace {
+
+constexpr int kEdgeWords = kReduceEdgeWords;   // per tile: lead[8], trail[8], meta, lead bad (the layout reserves 8 * kEdgeWords B)
+// meta: bit 0 the tile has a head, bit 2 the trail's group goes on past the tile, bit 3 trail bad,
+// bits 32.. the record index of the trail's head.  lead bad: a value of another length in the lead
+enum { E_LEAD = 0, E_TRAIL = 8, E_META = 16, E_LBAD = 17 };
+
+struct RSpec {       // travels in the kernel arguments; op of field f = (ops >> 8 f) & 0xFF, so no
+  uint64_t ops;      // kernel indexes an array with a run-time field number
+};
+
+__device__ __forceinline__ uint32_t r_op(const RSpec& sp, int f) { return (uint32_t)(sp.ops >> (8 * f)) & 0xFFu; }
+__device__ __forceinline__ uint64_t r_ident(uint32_t op) { return op == MTBLX_REDUCE_MIN ? ~0ull : 0ull; }
+__device__ __forceinline__ uint64_t r_apply(uint32_t op, uint64_t a, uint64_t b) {
+  return op == MTBLX_REDUCE_SUM ? a + b : op == MTBLX_REDUCE_MIN ? (a < b ? a : b) : (a > b ? a : b);
+}
+
+// a run of records: v = the fields reduced since the run's last head (or over the whole run if it
+// has none), fl bit 0 = the run has a head, bit 1 = a bad value since that head, hidx = that head
+template <int F>
+struct Seg {
+  uint64_t v[F];
+  uint32_t fl, hidx;
+};
+
+template <int F>
+__device__ __forceinline__ Seg<F> seg_ident(const RSpec& sp) {
+  Seg<F> r;
+#pragma unroll
+  for (int f = 0; f < F; ++f) r.v[f] = r_ident(r_op(sp, f));
+  r.fl = 0;
+  r.hidx = 0;
+  return r;
+}
+
+// run a followed by run b
+template <int F>
+__device__ __forceinline__ Seg<F> seg_join(const RSpec& sp, const Seg<F>& a, const Seg<F>& b) {
+  const bool cut = b.fl & 1u;
+  Seg<F> r;
+#pragma unroll
+  for (int f = 0; f < F; ++f) r.v[f] = cut ? b.v[f] : r_apply(r_op(sp, f), a.v[f], b.v[f]);
+  r.fl = cut ? b.fl : (a.fl | b.fl);
+  r.hidx = cut ? b.hidx : a.hidx;
+  return r;
+}
+
+template <int F>
+__device__ __forceinline__ Seg<F> seg_shfl_up(const Seg<F>& x, int o) {
+  Seg<F> r;
+#pragma unroll
+  for (int f = 0; f < F; ++f) r.v[f] = __shfl_up((unsigned long long)x.v[f], o, 64);
+  r.fl = __shfl_up(x.fl, o, 64);
+  r.hidx = __shfl_up(x.hidx, o, 64);
+  return r;
+}
+
+// the group's W bytes at vals + off, if they fit; -> false on overflow
+template <int F>
+__device__ __forceinline__ bool r_store(const mtblx_merged& o, uint64_t off, const uint64_t* v) {
+  if (off + 8u * F > o.vals_cap) return false;
+  MTBLX_CHK(o.vals + off, 8 * F);
+#pragma unroll
+  for (int f = 0; f < F; ++f) *reinterpret_cast<u64u*>(o.vals + off + 8 * f) = v[f];
+  return true;
+}
+
+template <int F>
+__global__ void __launch_bounds__(kThreads) k_reduce_tile(SrcTab t, const uint64_t* hdr, const Handle* h,
+                                                          const uint8_t* flag, const uint64_t* foff, mtblx_merged o,
+                                                          uint64_t* edges, RSpec sp, uint32_t n, uint64_t planned) {
+  if (hdr[H_PLANNED] != planned) return;   // k_merge_emit has reported it
+  __shared__ uint64_t wv[kThreads / 64][F];   // the waves' runs
+  __shared__ uint32_t wfl[kThreads / 64], whi[kThreads / 64];
+  constexpr uint64_t W = 8u * F;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint64_t tile0 = (uint64_t)blockIdx.x * kTile;
+  const uint64_t i0 = tile0 + (uint64_t)threadIdx.x * kPer;
+  // st: bit 0 head, bit 1 tail, bit 2 kept (in range and not dropped), bit 3 bad
+  uint64_t v[kPer][F];
+  uint32_t st[kPer];
+  bool anybad = false;
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    const uint64_t i = i0 + k;
+    st[k] = 0;
+#pragma unroll
+    for (int f = 0; f < F; ++f) v[k][f] = r_ident(r_op(sp, f));
+    if (i >= n) continue;
+    MTBLX_CHK(flag + i, 1);
+    const uint8_t fl = flag[i];
+    if (fl & 2) continue;
+    const bool head = fl & 1, tail = i + 1 == n || (flag[i + 1] & 1);
+    st[k] = (head ? 1u : 0u) | (tail ? 2u : 0u) | 4u;
+    if (head && tail) continue;   // a group of one: finished by k_merge_emit, whatever its length
+    MTBLX_CHK(h + i, 16);
+    const Handle c = h[i];
+    uint64_t vs;
+    const uint64_t vlen = val_len(t, c.src, c.idx, &vs);
+    if (vlen == W) {
+      const uint8_t* vp = t.s[c.src].vals + vs;   // any alignment
+#pragma unroll
+      for (int f = 0; f < F; ++f) v[k][f] = *reinterpret_cast<const u64u*>(vp + 8 * f);
+    } else {
+      st[k] |= 8u;
+      anybad = true;
+    }
+  }
+  if (anybad) atomicOr(o.flags, MTBLX_MERGE_BADVALUE);
+  // the thread's run, the wave's inclusive scan of the runs, the waves before this one
+  Seg<F> a = seg_ident<F>(sp);
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    if (!(st[k] & 4u)) continue;
+    Seg<F> e;
+#pragma unroll
+    for (int f = 0; f < F; ++f) e.v[f] = v[k][f];
+    e.fl = (st[k] & 1u) | ((st[k] & 8u) >> 2);
+    e.hidx = (uint32_t)(i0 + k);
+    a = seg_join<F>(sp, a, e);
+  }
+  Seg<F> x = a;
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const Seg<F> y = seg_shfl_up<F>(x, s);
+    if (lane >= s) x = seg_join<F>(sp, y, x);
+  }
+  if (lane == 63) {
+#pragma unroll
+    for (int f = 0; f < F; ++f) wv[w][f] = x.v[f];
+    wfl[w] = x.fl;
+    whi[w] = x.hidx;
+  }
+  Seg<F> acc = seg_shfl_up<F>(x, 1);   // the runs of the wave's lanes before this one
+  if (lane == 0) acc = seg_ident<F>(sp);
+  __syncthreads();
+  Seg<F> before = seg_ident<F>(sp);
+#pragma unroll
+  for (int k = 0; k < kThreads / 64 - 1; ++k)
+    if (k < w) {
+      Seg<F> y;
+#pragma unroll
+      for (int f = 0; f < F; ++f) y.v[f] = wv[k][f];
+      y.fl = wfl[k];
+      y.hidx = whi[k];
+      before = seg_join<F>(sp, before, y);
+    }
+  acc = seg_join<F>(sp, before, acc);   // everything of the tile before this thread's records
+  uint64_t* edge = edges + (uint64_t)blockIdx.x * kEdgeWords;
+  bool over = false;
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    if (!(st[k] & 4u)) continue;
+    const uint64_t i = i0 + k;
+    if ((st[k] & 1u) && !(acc.fl & 1u)) {   // the tile's first head: what came before it is the lead
+      MTBLX_CHK(edge + E_LEAD, 8 * F);
+#pragma unroll
+      for (int f = 0; f < F; ++f) edge[E_LEAD + f] = acc.v[f];
+      MTBLX_CHK(edge + E_LBAD, 8);
+      edge[E_LBAD] = (acc.fl >> 1) & 1u;
+    }
+    Seg<F> e;
+#pragma unroll
+    for (int f = 0; f < F; ++f) e.v[f] = v[k][f];
+    e.fl = (st[k] & 1u) | ((st[k] & 8u) >> 2);
+    e.hidx = (uint32_t)i;
+    acc = seg_join<F>(sp, acc, e);
+    if ((st[k] & 3u) == 2u && acc.fl == 1u) {   // the tail of a group of two or more, all of it here and good
+      MTBLX_CHK(foff + i, 8);
+      if (!r_store<F>(o, foff[i] - W, acc.v)) over = true;
+    }
+  }
+  if (over) atomicOr(o.flags, MTBLX_MERGE_OVERFLOW);
+  if (threadIdx.x == kThreads - 1) {   // acc: the whole tile (the threads past n bring nothing)
+    const uint64_t last = (tile0 + kTile < n ? tile0 + kTile : (uint64_t)n) - 1;
+    const bool has = acc.fl & 1u;
+    const bool open = has && last + 1 < n && !(flag[last + 1] & 1);
+    uint32_t m = has ? 1u : 0u;
+    if (has) {
+      m |= open ? 4u : 0u;
+      m |= (acc.fl & 2u) ? 8u : 0u;
+      MTBLX_CHK(edge + E_TRAIL, 8 * F);
+#pragma unroll
+      for (int f = 0; f < F; ++f) edge[E_TRAIL + f] = acc.v[f];
+    } else {
+      MTBLX_CHK(edge + E_LEAD, 8 * F);
+#pragma unroll
+      for (int f = 0; f < F; ++f) edge[E_LEAD + f] = acc.v[f];
+      MTBLX_CHK(edge + E_LBAD, 8);
+      edge[E_LBAD] = (acc.fl >> 1) & 1u;
+    }
+    MTBLX_CHK(edge + E_META, 8);
+    edge[E_META] = (uint64_t)m | ((uint64_t)acc.hidx << 32);
+  }
+}
+
+template <int F>
+__global__ void __launch_bounds__(kThreads) k_reduce_edges(const uint64_t* hdr, const uint64_t* foff, mtblx_merged o,
+                                                           const uint64_t* edges, RSpec sp, uint32_t ntiles,
+                                                           uint64_t planned) {
+  if (hdr[H_PLANNED] != planned) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t tile = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);   // the same for the whole wave
+  if (tile >= ntiles) return;
+  const uint64_t* mine = edges + tile * kEdgeWords;
+  MTBLX_CHK(mine + E_META, 8);
+  const uint64_t meta = mine[E_META];
+  if ((meta & 5u) != 5u) return;   // no head, or the trail's group ends with the tile
+  uint64_t p[F];
+  bool bad = meta & 8u;
+#pragma unroll
+  for (int f = 0; f < F; ++f) p[f] = lane == 0 ? mine[E_TRAIL + f] : r_ident(r_op(sp, f));
+  for (uint64_t base = tile + 1; base < ntiles; base += 64) {
+    const uint64_t u = base + lane;
+    const uint64_t* e = edges + u * kEdgeWords;
+    uint64_t m = 0;
+    if (u < ntiles) {
+      MTBLX_CHK(e + E_META, 8);
+      m = e[E_META];
+    }
+    const unsigned long long heads = __ballot(u < ntiles && (m & 1u));
+    const uint32_t first = heads ? (uint32_t)__builtin_ctzll(heads) : 64u;   // the lane whose tile ends the group
+    if (u < ntiles && lane <= first) {
+      bad = bad || e[E_LBAD];
+#pragma unroll
+      for (int f = 0; f < F; ++f) p[f] = r_apply(r_op(sp, f), p[f], e[E_LEAD + f]);
+    }
+    if (heads) break;
+  }
+#pragma unroll
+  for (int s = 32; s; s >>= 1) {
+#pragma unroll
+    for (int f = 0; f < F; ++f)
+      p[f] = r_apply(r_op(sp, f), p[f], (uint64_t)__shfl_xor((unsigned long long)p[f], s, 64));
+  }
+  if (__ballot(bad)) return;   // the records themselves have set MTBLX_MERGE_BADVALUE
+  if (lane == 0) {
+    const uint32_t hidx = (uint32_t)(meta >> 32);
+    MTBLX_CHK(foff + hidx, 8);
+    if (!r_store<F>(o, foff[hidx], p)) atomicOr(o.flags, MTBLX_MERGE_OVERFLOW);
+  }
+}
+
+// ---- host side ----
+// -> false if the spec is not one (mtblx_api.cpp has checked it already)
+inline bool reduce_spec(const mtblx_reduce* spec, RSpec* sp) {
+  if (!spec || spec->nfields < 1 || spec->nfields > MTBLX_REDUCE_MAX_FIELDS) return false;
+  sp->ops = 0;
+  for (uint32_t f = 0; f < spec->nfields; ++f) {
+    if (spec->op[f] > MTBLX_REDUCE_MAX) return false;
+    sp->ops |= (uint64_t)spec->op[f] << (8 * f);
+  }
+  return true;
+}
+
+template <int F>
+void reduce_launch_f(const SrcTab& t, uint8_t* w, const Layout& L, const Handle* hf, const mtblx_merged& o, RSpec sp,
+                     uint32_t n, uint64_t planned, hipStream_t s) {
+  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(w + L.hdr);
+  const uint64_t* foff = reinterpret_cast<const uint64_t*>(w + L.foff);
+  uint64_t* edges = reinterpret_cast<uint64_t*>(w + L.edges);
+  MTBLX_LAUNCH((MTBLX_R(w, L.total), MTBLX_R(o.vals, o.vals_cap), MTBLX_R(o.flags, 4)), k_reduce_tile<F>,
+               dim3(L.ntiles), dim3(kThreads), 0, s, t, hdr, hf, w + L.flag, foff, o, edges, sp, n, planned);
+  MTBLX_LAUNCH((MTBLX_R(w, L.total), MTBLX_R(o.vals, o.vals_cap), MTBLX_R(o.flags, 4)), k_reduce_edges<F>,
+               dim3((L.ntiles + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, s, hdr, foff, o, edges, sp,
+               L.ntiles, planned);
+}
+
+// after k_merge_emit in FIRST mode on the same stream; n != 0
+void reduce_launch(const SrcTab& t, uint8_t* w, const Layout& L, const Handle* hf, const mtblx_merged& o, RSpec sp,
+                   uint32_t nfields, uint32_t n, uint64_t planned, hipStream_t s) {
+  switch (nfields) {
+    case 1: reduce_launch_f<1>(t, w, L, hf, o, sp, n, planned, s); break;
+    case 2: reduce_launch_f<2>(t, w, L, hf, o, sp, n, planned, s); break;
+    case 3: reduce_launch_f<3>(t, w, L, hf, o, sp, n, planned, s); break;
+    case 4: reduce_launch_f<4>(t, w, L, hf, o, sp, n, planned, s); break;
+    case 5: reduce_launch_f<5>(t, w, L, hf, o, sp, n, planned, s); break;
+    case 6: reduce_launch_f<6>(t, w, L, hf, o, sp, n, planned, s); break;
+    case 7: reduce_launch_f<7>(t, w, L, hf, o, sp, n, planned, s); break;
+    default: reduce_launch_f<8>(t, w, L, hf, o, sp, n, planned, s); break;
+  }
+}
+
+}  // namespace

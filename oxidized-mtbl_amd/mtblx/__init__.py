@@ -7,8 +7,10 @@ Package layout
   synth.py    deterministic synthetic workloads of BASELINE.json's configs
   merger.py   Merger / MergerBuilder mirror of src/merger.rs over the device merge (csrc/merge.hip)
   sorter.py   Sorter / SorterBuilder mirror of src/sorter.rs over the device sort (csrc/sort.hip)
+  reduce.py   Reduce / MergeError: u64 sum / min / max merge functions evaluated on the device (csrc/reduce_dev.h)
 """
 from ._lib import EXPORTS, LIB_PATH, lib  # noqa: F401
+from .reduce import MergeError, Reduce  # noqa: F401
 from .writer import CompressionType, OutOfOrderKey, Writer, WriterBuilder  # noqa: F401
 
 
@@ -23,4 +25,4 @@ def __getattr__(name):   # Merger / MergerBuilder / Sorter / SorterBuilder need 
 
 
 __all__ = ["Writer", "WriterBuilder", "CompressionType", "OutOfOrderKey", "Merger", "MergerBuilder", "Sorter", "SorterBuilder",
-           "lib", "LIB_PATH", "EXPORTS"]
+           "Reduce", "MergeError", "lib", "LIB_PATH", "EXPORTS"]

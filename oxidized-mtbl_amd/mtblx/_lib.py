@@ -44,6 +44,7 @@ EXPORTS = [
     "mtblx_key_filter",
     "mtblx_merge_workspace_bytes", "mtblx_merge_plan", "mtblx_merge_emit", "mtblx_merge_plan_timed",
     "mtblx_sort_workspace_bytes", "mtblx_sort_plan", "mtblx_sort_emit", "mtblx_sort_plan_timed",
+    "mtblx_merge_emit_reduce", "mtblx_sort_emit_reduce",
     "mtblx_snappy_compress_workspace_bytes", "mtblx_snappy_slots", "mtblx_snappy_compress_dev", "mtblx_frame_blocks",
     "mtblx_encode_index_c",
     "mtblx_scan_workspace_bytes", "mtblx_scan_plan", "mtblx_scan_emit",
@@ -54,6 +55,9 @@ MERGE_MAX_SOURCES, MERGE_MAX_RECORDS = 64, (1 << 32) - 16
 MERGE_GROUPS, MERGE_CONCAT, MERGE_FIRST, MERGE_LAST = range(4)
 MERGE_UNSORTED, MERGE_INTERNAL = 1, 2          # totals[5] of mtblx_merge_plan
 MERGE_OVERFLOW, MERGE_NOT_PLANNED = 1, 2       # *flags of mtblx_merge_emit
+MERGE_BADVALUE = 4                             # *flags of mtblx_merge_emit_reduce / mtblx_sort_emit_reduce
+REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)  # mtblx_reduce.op
+REDUCE_MAX_FIELDS = 8
 SORT_TILE = 1024                               # MTBLX_SORT_TILE: handles per tile-sorted run of mtblx_sort_plan
 PLAN_OUT_OF_ORDER, PLAN_PANIC, PLAN_TOO_LONG = 1, 2, 4
 SCAN_OK, SCAN_LARGE, SCAN_FALLBACK = range(3)  # mtblx_scan_result.status
@@ -83,6 +87,10 @@ class Merged(C.Structure):   # mtblx_merged (capacities in bytes)
     _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("key_end", C.c_void_p), ("key_end_cap", C.c_uint64),
                 ("vals", C.c_void_p), ("vals_cap", C.c_uint64), ("val_end", C.c_void_p), ("val_end_cap", C.c_uint64),
                 ("grp_end", C.c_void_p), ("grp_end_cap", C.c_uint64), ("flags", C.c_void_p)]
+
+
+class ReduceSpec(C.Structure):   # mtblx_reduce
+    _fields_ = [("nfields", C.c_uint32), ("op", C.c_uint8 * 8)]
 
 
 class ScanResult(C.Structure):   # mtblx_scan_result
@@ -305,6 +313,12 @@ def lib() -> C.CDLL:
         L.mtblx_sort_emit.argtypes = [C.POINTER(Records), C.c_int, C.POINTER(Merged), C.c_void_p, C.c_size_t,
                                       C.c_void_p]
         L.mtblx_sort_emit.restype = C.c_int
+        L.mtblx_merge_emit_reduce.argtypes = [C.POINTER(Records), C.c_uint32, C.POINTER(ReduceSpec), C.POINTER(Merged),
+                                              C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_merge_emit_reduce.restype = C.c_int
+        L.mtblx_sort_emit_reduce.argtypes = [C.POINTER(Records), C.POINTER(ReduceSpec), C.POINTER(Merged), C.c_void_p,
+                                             C.c_size_t, C.c_void_p]
+        L.mtblx_sort_emit_reduce.restype = C.c_int
         L.mtblx_scan_workspace_bytes.argtypes = [C.c_uint32]
         L.mtblx_scan_workspace_bytes.restype = C.c_size_t
         _file = [C.c_void_p, C.c_uint64, C.c_uint32]                                    # file, file_len, version

@@ -9,7 +9,8 @@
 Every source is scanned on the device (Reader.iter()), and its records never leave it: the
 k-way merge, the grouping of duplicate keys and the gather of the merged records are
 mtblx_merge_plan / mtblx_merge_emit (include/mtblx.h, csrc/merge.hip).  The built-in merge
-functions "concat", "first" and "last" produce an encode.DeviceRecords that feeds
+functions "concat", "first" and "last" and a reduce.Reduce (u64 sum / min / max per field,
+mtblx_merge_emit_reduce) produce an encode.DeviceRecords that feeds
 encode.write_file as it is; a callable ``merge(key, values) -> bytes`` is applied on the host to
 the groups of two or more values, as the reference never calls it for a group of one (:200-207).
 
@@ -28,6 +29,7 @@ import torch
 
 from . import _lib, codec, encode
 from .encode import DeviceRecords
+from .reduce import MergeError, Reduce, as_reduce, check_merge  # noqa: F401
 from .writer import CompressionType
 
 MODES = {"groups": _lib.MERGE_GROUPS, "concat": _lib.MERGE_CONCAT, "first": _lib.MERGE_FIRST,
@@ -76,14 +78,17 @@ def _records_list(r: DeviceRecords):
     return out
 
 
-def merge_records(sources, mode: str, stream=None, device=None):
+def merge_records(sources, mode, stream=None, device=None):
     """One mtblx_merge_plan + mtblx_merge_emit over at most 64 sources (DeviceRecords, in source
-    order) -> Grouped for "groups", else DeviceRecords.  Workspace and outputs are allocated on
-    the stream the kernels run on."""
+    order) -> Grouped for "groups", else DeviceRecords.  `mode` is a name of MODES, or a Reduce (or
+    its shorthand name): then the emit is mtblx_merge_emit_reduce, with "first"'s layout, and a
+    group of two or more holding a value of another length raises MergeError.  Workspace and
+    outputs are allocated on the stream the kernels run on."""
     L = codec._require_device()
     if len(sources) > _lib.MERGE_MAX_SOURCES:
         raise ValueError("merge_records takes at most 64 sources (Merger merges in rounds)")
-    m = MODES[mode]
+    red = as_reduce(mode)
+    m = _lib.MERGE_FIRST if red is not None else MODES[mode]
     dev = torch.device(device) if device is not None else (sources[0].key_end.device if sources else
                                                           torch.device("cuda", torch.cuda.current_device()))
     s = stream if stream is not None else torch.cuda.current_stream(dev)
@@ -117,10 +122,16 @@ def merge_records(sources, mode: str, stream=None, device=None):
         u = codec._u
         out = _lib.Merged(u(keys), kbytes, u(key_end), 8 * groups, u(vals), vbytes, u(val_end), 8 * val_end.numel(),
                           u(grp_end), 8 * grp_end.numel(), flags.data_ptr())
-        rc = L.mtblx_merge_emit(arr, nsrc, m, C.byref(out), C.c_void_p(wp), wsb, sh)
+        if red is not None:
+            spec = red.cstruct()
+            rc = L.mtblx_merge_emit_reduce(arr, nsrc, C.byref(spec), C.byref(out), C.c_void_p(wp), wsb, sh)
+        else:
+            rc = L.mtblx_merge_emit(arr, nsrc, m, C.byref(out), C.c_void_p(wp), wsb, sh)
         if rc != 0:
             raise RuntimeError(f"mtblx_merge_emit failed: {rc}")
         f = int(flags.item())   # synchronizes: the workspace may go back to the allocator after this
+        if f & _lib.MERGE_BADVALUE:
+            raise MergeError(f"merge: a group of two or more holds a value that is not {red.width} bytes long")
         if f:
             raise RuntimeError(f"mtblx_merge_emit: flags={f}")
         if m in (_lib.MERGE_FIRST, _lib.MERGE_LAST) and groups:   # vals was sized by its upper bound
@@ -148,9 +159,10 @@ def _regroup(parts, stream):
     return Grouped(va.keys, va.key_end, va.vals, torch.cumsum(lens, 0), vb.val_end // 8)
 
 
-def merge_all(sources, mode: str, stream=None, device=None):
+def merge_all(sources, mode, stream=None, device=None):
     """merge_records over any number of sources: rounds of 64 with the same mode, which keeps
-    source order (and with it the exact result) for every mode."""
+    source order (and with it the exact result) for every mode; a Reduce is associative and
+    passes a group of one through, so applying it per round gives the same bytes too."""
     sources = list(sources)
     grouped = mode == "groups"
     first = True
@@ -181,12 +193,11 @@ def _scan_records(reader) -> DeviceRecords:
 
 
 class MergerBuilder:
-    """src/merger.rs:66-94.  merge: "concat" | "first" | "last" | callable(key, values) -> bytes"""
+    """src/merger.rs:66-94.  merge: "concat" | "first" | "last" | Reduce (or "sum_u64" | "min_u64" |
+    "max_u64") | callable(key, values) -> bytes"""
 
     def __init__(self, merge):
-        if not callable(merge) and merge not in ("concat", "first", "last"):
-            raise ValueError(f"merge: {merge!r}")
-        self._merge = merge
+        self._merge = check_merge(merge)
         self._sources = []
 
     def add(self, source) -> "MergerBuilder":
@@ -207,7 +218,7 @@ class MergerBuilder:
 class Merger:
     def __init__(self, sources, merge, stream=None):
         self.sources = sources
-        self.merge = merge
+        self.merge = check_merge(merge)
         self.stream = stream
 
     @staticmethod

@@ -20,7 +20,8 @@ What differs from the reference, on purpose:
   * the values of a key come out in insertion order (the reference sorts with sort_unstable_by and
     drains a BinaryHeap: it promises only the multiset).  A merged chunk counts as the oldest
     source of every later merge, which keeps that order across ``merge_chunks``.
-For the built-in merge functions no record returns to the host between ``insert`` and the file; a
+For the built-in merge functions and for a reduce.Reduce (u64 sum / min / max per field, reduced on
+the device per chunk and again over the chunks) no record returns to the host between ``insert`` and the file; a
 callable ``merge(key, values) -> bytes`` is applied on the host to the groups of two or more
 values, never to a group of one (:166-170).
 """
@@ -34,6 +35,7 @@ import torch
 from . import _lib, codec, encode
 from .encode import DeviceRecords
 from .merger import MODES, Grouped, _records_list, merge_all  # noqa: F401  (merge_all: looked up here at call time)
+from .reduce import MergeError, Reduce, as_reduce, check_merge  # noqa: F401
 from .writer import CompressionType
 
 DEFAULT_NB_CHUNKS, MIN_NB_CHUNKS = 25, 1                              # src/lib.rs:11-12
@@ -43,13 +45,16 @@ DEFAULT_COMPRESSION_LEVEL = 0                                         # :8
 ENTRY_SIZE = 32   # size_of::<Entry>() on 64-bit: a Vec<u8> (24) + key_len (8), src/sorter.rs:72-75
 
 
-def sort_records(recs: DeviceRecords, mode: str, stream=None):
+def sort_records(recs: DeviceRecords, mode, stream=None):
     """One mtblx_sort_plan + mtblx_sort_emit over one batch of records in any order -> Grouped for
     "groups", else DeviceRecords: keys ascending, one item per distinct key, the values of a key in
-    input order, the empty-key group kept (no quirk here).  Workspace and outputs are allocated on
-    the stream the kernels run on."""
+    input order, the empty-key group kept (no quirk here).  `mode` is a name of MODES, or a Reduce
+    (or its shorthand name): then the emit is mtblx_sort_emit_reduce, with "first"'s layout, and a
+    group of two or more holding a value of another length raises MergeError.  Workspace and
+    outputs are allocated on the stream the kernels run on."""
     L = codec._require_device()
-    m = MODES[mode]
+    red = as_reduce(mode)
+    m = _lib.MERGE_FIRST if red is not None else MODES[mode]
     dev = recs.key_end.device
     s = stream if stream is not None else torch.cuda.current_stream(dev)
     with torch.cuda.stream(s):   # the caching allocator ties these blocks to the stream that uses them
@@ -76,10 +81,16 @@ def sort_records(recs: DeviceRecords, mode: str, stream=None):
         u = codec._u
         out = _lib.Merged(u(keys), kbytes, u(key_end), 8 * groups, u(vals), vbytes, u(val_end), 8 * val_end.numel(),
                           u(grp_end), 8 * grp_end.numel(), flags.data_ptr())
-        rc = L.mtblx_sort_emit(C.byref(rec), m, C.byref(out), C.c_void_p(wp), wsb, sh)
+        if red is not None:
+            spec = red.cstruct()
+            rc = L.mtblx_sort_emit_reduce(C.byref(rec), C.byref(spec), C.byref(out), C.c_void_p(wp), wsb, sh)
+        else:
+            rc = L.mtblx_sort_emit(C.byref(rec), m, C.byref(out), C.c_void_p(wp), wsb, sh)
         if rc != 0:
             raise RuntimeError(f"mtblx_sort_emit failed: {rc}")
         f = int(flags.item())   # synchronizes: the workspace may go back to the allocator after this
+        if f & _lib.MERGE_BADVALUE:
+            raise MergeError(f"merge: a group of two or more holds a value that is not {red.width} bytes long")
         if f:
             raise RuntimeError(f"mtblx_sort_emit: flags={f}")
         if m in (_lib.MERGE_FIRST, _lib.MERGE_LAST) and groups:   # vals was sized by its upper bound
@@ -96,13 +107,12 @@ def _apply(merge, grouped: Grouped, device) -> DeviceRecords:
 
 
 class SorterBuilder:
-    """src/sorter.rs:25-70.  merge: "concat" | "first" | "last" | callable(key, values) -> bytes.
+    """src/sorter.rs:25-70.  merge: "concat" | "first" | "last" | Reduce (or "sum_u64" | "min_u64" |
+    "max_u64") | callable(key, values) -> bytes.
     Chunks stay in device memory, so the two chunk_compression settings are stored and unused."""
 
     def __init__(self, merge, device="cuda", stream=None):
-        if not callable(merge) and merge not in ("concat", "first", "last"):
-            raise ValueError(f"merge: {merge!r}")
-        self._merge = merge
+        self._merge = check_merge(merge)
         self._device, self._stream = device, stream
         self._max_memory = DEFAULT_SORTER_MEMORY                  # :28
         self._max_nb_chunks = DEFAULT_NB_CHUNKS                   # :29
@@ -137,9 +147,7 @@ class Sorter:
     merges: how often merge_chunks ran."""
 
     def __init__(self, merge, device="cuda", stream=None):   # Sorter::new (:112-114)
-        if not callable(merge) and merge not in ("concat", "first", "last"):
-            raise ValueError(f"merge: {merge!r}")
-        self.merge = merge
+        self.merge = check_merge(merge)
         self.device, self.stream = torch.device(device), stream
         self.max_memory, self.max_nb_chunks = DEFAULT_SORTER_MEMORY, DEFAULT_NB_CHUNKS
         self.chunk_compression_type, self.chunk_compression_level = CompressionType.Snappy, DEFAULT_COMPRESSION_LEVEL
