@@ -15,6 +15,8 @@
 //   Metadata                    src/metadata.rs:11-24
 //   MergerBuilder / Merger      src/merger.rs:66-260                    (mtblx_merge_plan / _emit: the k-way
 //                                                                        merge and the grouping on the device)
+//   Merger::scan_batch          (not in the crate: MergerIter over iter_from / get / iter_prefix / iter_range
+//                                of every source for a batch of queries; mtblx_merge_seg_plan / _emit)
 //   SorterBuilder / Sorter      src/sorter.rs:17-258                    (mtblx_sort_plan / _emit: the sort of
 //                                                                        a chunk on the device; the chunks
 //                                                                        merged by the device Merger)
@@ -1380,9 +1382,12 @@ inline HostGroups merge_once(const std::vector<HostGroups>& src, size_t i0, size
   return r;
 }
 // grouped results of consecutive source chunks -> the grouped result of all their sources: the
-// groups' value bytes joined per key (CONCAT), and the groups' value lengths joined the same way
-inline HostGroups regroup(const std::vector<HostGroups>& parts, size_t i0, size_t i1) {
-  std::vector<HostGroups> a(i1 - i0), b(i1 - i0);
+// groups' value bytes joined per key (CONCAT), and the groups' value lengths joined the same way.
+// regroup_split makes the two CONCAT inputs of parts [i0, i1), regroup_join the result of the two merges
+inline void regroup_split(const std::vector<HostGroups>& parts, size_t i0, size_t i1, std::vector<HostGroups>& a,
+                          std::vector<HostGroups>& b) {
+  a.assign(i1 - i0, HostGroups());
+  b.assign(i1 - i0, HostGroups());
   for (size_t i = i0; i < i1; ++i) {
     const HostGroups& p = parts[i];
     HostGroups &x = a[i - i0], &y = b[i - i0];
@@ -1399,8 +1404,8 @@ inline HostGroups regroup(const std::vector<HostGroups>& parts, size_t i0, size_
       std::memcpy(y.vals.data() + 8 * j, &len, 8);
     }
   }
-  HostGroups va = merge_once(a, 0, a.size(), MTBLX_MERGE_CONCAT);
-  const HostGroups vb = merge_once(b, 0, b.size(), MTBLX_MERGE_CONCAT);
+}
+inline HostGroups regroup_join(HostGroups va, const HostGroups& vb) {
   HostGroups r;
   r.keys = std::move(va.keys);
   r.ke = std::move(va.ke);
@@ -1413,6 +1418,12 @@ inline HostGroups regroup(const std::vector<HostGroups>& parts, size_t i0, size_
   }
   for (uint64_t e : vb.ve) r.ge.push_back(e / 8);
   return r;
+}
+inline HostGroups regroup(const std::vector<HostGroups>& parts, size_t i0, size_t i1) {
+  std::vector<HostGroups> a, b;
+  regroup_split(parts, i0, i1, a, b);
+  HostGroups va = merge_once(a, 0, a.size(), MTBLX_MERGE_CONCAT);
+  return regroup_join(std::move(va), merge_once(b, 0, b.size(), MTBLX_MERGE_CONCAT));
 }
 inline HostGroups merge_all(std::vector<HostGroups> src, int mode, const mtblx_reduce* rd = nullptr) {
   bool first = true;
@@ -1429,6 +1440,103 @@ inline HostGroups merge_all(std::vector<HostGroups> src, int mode, const mtblx_r
 }
 inline Bytes slice(const Bytes& b, const std::vector<uint64_t>& end, size_t i) {
   return Bytes(b.begin() + (i ? end[i - 1] : 0), b.begin() + end[i]);
+}
+
+// ---- the segmented merge (mtblx_merge_seg_plan / _emit, csrc/merge_seg.hip): every source is nseg
+// sorted runs back to back, cut by off[i] (nseg + 1 offsets); segment q of the result is the merge
+// of segment q of every source, its groups [seg_end[q-1], seg_end[q])
+struct SegGroups {
+  HostGroups g;
+  std::vector<uint64_t> seg_end;
+};
+using SegOffsets = std::vector<std::vector<uint64_t>>;
+// one plan + emit over sources [i0, i1) (at most MTBLX_MERGE_MAX_SOURCES), as merge_once
+inline SegGroups merge_seg_once(const std::vector<HostGroups>& src, const SegOffsets& off, size_t i0, size_t i1,
+                                uint32_t nseg, int mode, const mtblx_reduce* rd = nullptr) {
+  const uint32_t ns = static_cast<uint32_t>(i1 - i0);
+  std::vector<DevBuf> bufs;
+  std::vector<mtblx_records> recs(ns ? ns : 1);
+  std::vector<const uint64_t*> offp(ns ? ns : 1, nullptr);
+  uint64_t n = 0;
+  for (uint32_t i = 0; i < ns; ++i) {
+    const HostGroups& s = src[i0 + i];
+    if (off[i0 + i].size() != (size_t)nseg + 1) throw std::invalid_argument("merge: nseg + 1 offsets per source");
+    bufs.push_back(upload(s.keys.data(), s.keys.size()));
+    bufs.push_back(upload(s.ke.data(), s.ke.size()));
+    bufs.push_back(upload(s.vals.data(), s.vals.size()));
+    bufs.push_back(upload(s.ve.data(), s.ve.size()));
+    bufs.push_back(upload(off[i0 + i].data(), off[i0 + i].size()));
+    const size_t b = bufs.size() - 5;
+    recs[i] = mtblx_records{bufs[b].as<uint8_t>(), bufs[b + 1].as<uint64_t>(), bufs[b + 2].as<uint8_t>(),
+                            bufs[b + 3].as<uint64_t>(), s.ke.size()};
+    offp[i] = bufs[b + 4].as<uint64_t>();
+    n += s.ke.size();
+  }
+  const size_t wsb = mtblx_merge_seg_workspace_bytes(n, ns, nseg);
+  if (!wsb) throw std::length_error("merge: 2^32 - 16 records or more, or more than 2^24 queries");
+  DevBuf ws(wsb), se(8 * (size_t)nseg);
+  uint64_t tot[6] = {};
+  const int rc = mtblx_merge_seg_plan(recs.data(), offp.data(), ns, nseg, tot, se.as<uint64_t>(), ws.p, wsb, nullptr);
+  if (rc == MTBLX_E_FORMAT && !(tot[5] & MTBLX_MERGE_BADSEG)) throw UnsortedSource();
+  abi_check(rc, "mtblx_merge_seg_plan");
+  const bool grouped = mode == MTBLX_MERGE_GROUPS;
+  const uint64_t nve = grouped ? tot[2] : tot[0], nge = grouped ? tot[0] : 0;
+  DevBuf k(tot[1]), ke(8 * tot[0]), v(tot[3]), ve(8 * nve), ge(8 * nge), fl(4);
+  const mtblx_merged out{k.as<uint8_t>(),  tot[1],  ke.as<uint64_t>(), 8 * tot[0], v.as<uint8_t>(), tot[3],
+                         ve.as<uint64_t>(), 8 * nve, ge.as<uint64_t>(), 8 * nge,    fl.as<uint32_t>()};
+  if (rd)
+    abi_check(mtblx_merge_seg_emit_reduce(recs.data(), offp.data(), ns, nseg, rd, &out, ws.p, wsb, nullptr),
+              "mtblx_merge_seg_emit_reduce");
+  else
+    abi_check(mtblx_merge_seg_emit(recs.data(), offp.data(), ns, nseg, mode, &out, ws.p, wsb, nullptr),
+              "mtblx_merge_seg_emit");
+  hip_check(hipDeviceSynchronize(), "sync");
+  const uint32_t flags = download<uint32_t>(fl.p, 1)[0];
+  if (flags & MTBLX_MERGE_BADVALUE) throw MergeError();
+  if (flags) throw std::runtime_error("mtblx_merge_seg_emit: flags set");
+  SegGroups r;
+  r.seg_end = download<uint64_t>(se.p, nseg);
+  r.g.ke = download<uint64_t>(ke.p, tot[0]);
+  r.g.ve = download<uint64_t>(ve.p, nve);
+  r.g.ge = download<uint64_t>(ge.p, nge);
+  r.g.keys = download<uint8_t>(k.p, tot[1]);
+  r.g.vals = download<uint8_t>(v.p, r.g.ve.empty() ? 0 : r.g.ve.back());
+  return r;
+}
+// any number of sources: rounds of MTBLX_MERGE_MAX_SOURCES with the same mode, a round's output cut
+// by {0, seg_end...} being a source of the next; GROUPS through the two CONCATs of regroup
+inline SegGroups merge_seg_all(std::vector<HostGroups> src, SegOffsets off, uint32_t nseg, int mode,
+                               const mtblx_reduce* rd = nullptr) {
+  bool first = true;
+  while (first || src.size() > 1) {
+    std::vector<HostGroups> next;
+    SegOffsets noff;
+    for (size_t i = 0; i < src.size() || (first && src.empty() && next.empty()); i += MTBLX_MERGE_MAX_SOURCES) {
+      const size_t e = std::min(src.size(), i + MTBLX_MERGE_MAX_SOURCES);
+      SegGroups r;
+      if (mode == MTBLX_MERGE_GROUPS && !first) {
+        std::vector<HostGroups> a, b;
+        regroup_split(src, i, e, a, b);
+        const SegOffsets o(off.begin() + i, off.begin() + e);
+        SegGroups va = merge_seg_once(a, o, 0, a.size(), nseg, MTBLX_MERGE_CONCAT);
+        r.g = regroup_join(std::move(va.g), merge_seg_once(b, o, 0, b.size(), nseg, MTBLX_MERGE_CONCAT).g);
+        r.seg_end = std::move(va.seg_end);
+      } else {
+        r = merge_seg_once(src, off, i, e, nseg, mode, rd);
+      }
+      std::vector<uint64_t> o(1, 0);
+      o.insert(o.end(), r.seg_end.begin(), r.seg_end.end());
+      next.push_back(std::move(r.g));
+      noff.push_back(std::move(o));
+    }
+    src = std::move(next);
+    off = std::move(noff);
+    first = false;
+  }
+  SegGroups r;
+  r.g = std::move(src[0]);
+  r.seg_end.assign(off[0].begin() + 1, off[0].end());
+  return r;
 }
 }  // namespace detail
 
@@ -1488,9 +1596,87 @@ class Merger {
   void write_into(Writer& w) const {
     for (const auto& kv : into_merge_iter()) w.insert(kv.first, kv.second);
   }
+  // MergerIter over iter_from / get / iter_prefix / iter_range of every source, for a batch of
+  // queries: out[q] is what into_merge_iter would yield if each source were opened with query q,
+  // the empty-key quirk applied inside the query (mtblx.h "Segmented merge").  Every source answers
+  // the batch with Reader::scan_batch; the queries the kernels served in every source are merged
+  // by ONE segmented merge (mtblx_merge_seg_plan / _emit; rounds of 64 sources), the others
+  // (max_blocks, a compressed source, an irregular index) by the Merger's merge over the per-source
+  // answers.  A query's max_records = m keeps the first m items of its unlimited result: every
+  // source is asked for m + 1 records (a source's record at position p >= m + 1 has at least
+  // p - 1 >= m distinct kept keys before it; the - 1 is the empty key the quirk may drop).  With a
+  // MergeReduce, MergeError is thrown iff a bad group lies among the at most S * (m + 1) records
+  // fetched for a query.  served (may be null): per query, 1 where the segmented merge answered it.
+  std::vector<std::vector<std::pair<Bytes, Bytes>>> scan_batch(const std::vector<ScanQuery>& queries,
+                                                                uint32_t max_blocks = 64,
+                                                                std::vector<uint8_t>* served = nullptr) const {
+    const uint32_t nq = static_cast<uint32_t>(queries.size());
+    const size_t ns = sources_.size();
+    std::vector<ScanQuery> ask = queries;
+    for (ScanQuery& q : ask)
+      if (q.max_records && *q.max_records != ~0ull) q.max_records = *q.max_records + 1;
+    std::vector<std::vector<Reader::Records>> ans(ns);
+    std::vector<uint8_t> kernel(nq, 1);
+    for (size_t s = 0; s < ns; ++s) {
+      std::vector<uint8_t> sv;
+      ans[s] = sources_[s].scan_batch(ask, max_blocks, &sv);
+      for (uint32_t q = 0; q < nq; ++q) kernel[q] &= sv[q];
+    }
+    const mtblx_reduce* rd = reduce_ ? &rd_ : nullptr;
+    std::vector<detail::HostGroups> src(ns);
+    detail::SegOffsets off(ns);
+    for (size_t s = 0; s < ns; ++s) {
+      off[s].push_back(0);
+      for (uint32_t q = 0; q < nq; ++q) {
+        if (kernel[q]) append(src[s], ans[s][q]);
+        off[s].push_back(src[s].ke.size());
+      }
+    }
+    const detail::SegGroups m = detail::merge_seg_all(std::move(src), std::move(off), nq, mode_, rd);
+    std::vector<std::vector<std::pair<Bytes, Bytes>>> out(nq);
+    for (uint32_t q = 0; q < nq; ++q) {
+      const uint64_t lim = queries[q].max_records ? *queries[q].max_records : ~0ull;
+      if (kernel[q]) {
+        const uint64_t g0 = q ? m.seg_end[q - 1] : 0;
+        out[q] = items(m.g, g0, g0 + std::min<uint64_t>(lim, m.seg_end[q] - g0));   // the cut is a view
+        continue;
+      }
+      std::vector<detail::HostGroups> one(ns);
+      for (size_t s = 0; s < ns; ++s) append(one[s], ans[s][q]);
+      const detail::HostGroups g = detail::merge_all(std::move(one), mode_, rd);
+      out[q] = items(g, 0, std::min<uint64_t>(lim, g.ke.size()));
+    }
+    if (served) *served = std::move(kernel);
+    return out;
+  }
 
  private:
   friend class MergerBuilder;
+  static void append(detail::HostGroups& s, const Reader::Records& recs) {
+    for (const auto& kv : recs) {
+      s.keys.insert(s.keys.end(), kv.first.begin(), kv.first.end());
+      s.vals.insert(s.vals.end(), kv.second.begin(), kv.second.end());
+      s.ke.push_back(s.keys.size());
+      s.ve.push_back(s.vals.size());
+    }
+  }
+  // MergerIter's items [g0, g1) of a result in this Merger's mode: the merge function runs on the
+  // host for the groups of two or more, as in into_merge_iter
+  std::vector<std::pair<Bytes, Bytes>> items(const detail::HostGroups& g, uint64_t g0, uint64_t g1) const {
+    std::vector<std::pair<Bytes, Bytes>> out;
+    for (uint64_t i = g0; i < g1; ++i) {
+      if (mode_ != MTBLX_MERGE_GROUPS) {
+        out.emplace_back(detail::slice(g.keys, g.ke, i), detail::slice(g.vals, g.ve, i));
+        continue;
+      }
+      std::vector<Bytes> vs;
+      for (uint64_t j = i ? g.ge[i - 1] : 0; j < g.ge[i]; ++j) vs.push_back(detail::slice(g.vals, g.ve, j));
+      Bytes k = detail::slice(g.keys, g.ke, i);
+      Bytes v = vs.size() == 1 ? std::move(vs[0]) : fn_(k, vs);
+      out.emplace_back(std::move(k), std::move(v));
+    }
+    return out;
+  }
   Merger(int mode, MergeFn fn, std::vector<Reader> s, const mtblx_reduce& rd, bool reduce)
       : mode_(mode), fn_(std::move(fn)), rd_(rd), reduce_(reduce), sources_(std::move(s)) {}
   detail::HostGroups run(int mode) const {

@@ -740,6 +740,62 @@ int mtblx_merge_emit_reduce(const mtblx_records* src, uint32_t nsrc, const mtblx
 int mtblx_sort_emit_reduce(const mtblx_records* in, const mtblx_reduce* spec, const mtblx_merged* out,
                            void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- Segmented merge: the Merger over a batch of scan results (csrc/merge_seg.hip) ----
+ * Every source is nseg sorted runs back to back: source s's records [seg_off[s][q], seg_off[s][q+1])
+ * belong to segment q (seg_off: host array [nsrc] of device arrays [nseg + 1], u64, with
+ * 0 = off[0] <= ... <= off[nseg] = src[s].n).  That is the shape of nsrc results of mtblx_scan_emit
+ * over the same nq = nseg queries (the records plus rec_off): the segments come in any order and may
+ * overlap; keys are strictly increasing INSIDE a segment only.  Segment q of the output is what
+ * mtblx_merge_plan / _emit give over segment q of every source: one item per distinct key of the
+ * segment, the values of a group in source order, and the empty-key quirk applied per segment (an
+ * empty-key record is kept iff it is the last record of its segment's merged order; when only
+ * empty keys match, one item ("", [v]) with the highest-numbered source's v).  This is the read
+ * path of a merged view: MergerIter / MultiIter (src/merger.rs:159-260) as they would run if
+ * into_merge_iter built each Entry from iter_from / iter_prefix / iter_range / get of the source.
+ *  - Output: one mtblx_merged in (segment, key) order; the groups of segment q are
+ *    [seg_end[q-1], seg_end[q]) (seg_end: device [nseg], END group indices; 0 before segment 0).
+ *    Modes, capacities, *flags, MTBLX_MERGE_NOT_PLANNED and totals[0..5] are exactly
+ *    mtblx_merge_emit's and mtblx_merge_plan's (totals[4] counts the quirk's drops over all
+ *    segments); in the three single-value modes the output is an mtblx_records as it stands.
+ *    mtblx_merge_seg_emit_reduce is mtblx_merge_emit_reduce over the same plan.
+ *  - seg_off is validated on the device before anything is indexed with it: a bad array gives
+ *    MTBLX_E_FORMAT with MTBLX_MERGE_BADSEG in totals[5]; an out-of-order pair inside a segment gives
+ *    MTBLX_E_FORMAT with MTBLX_MERGE_UNSORTED.  Both are read back before any merge pass (other
+ *    totals 0).  The same two keys out of order in DIFFERENT segments are fine.
+ *  - Limits: nsrc <= MTBLX_MERGE_MAX_SOURCES (more: merge in rounds with the same mode; a round's
+ *    output with {0, seg_end...} as its seg_off is a source of the next), nseg <=
+ *    MTBLX_MERGE_MAX_SEGMENTS, fewer than MTBLX_MERGE_MAX_RECORDS records in all sources together.
+ *    nseg == 0, nsrc == 0 and empty sources are legal and give zero totals (seg_off may be NULL
+ *    when nsrc == 0).
+ *  - MTBLX_E_INVAL before any device call: NULL or misaligned workspace, ws_bytes below
+ *    mtblx_merge_seg_workspace_bytes, nsrc or nseg above the limits, too many records, NULL src /
+ *    seg_off / seg_off[s] (nsrc != 0), NULL totals, NULL seg_end (nseg != 0), and everything
+ *    mtblx_merge_emit / mtblx_merge_emit_reduce refuse.
+ * How: the Merger's 16-byte handle with the segment in the upper 26 bits of its source word,
+ * ordered by (segment, key, source), so each source's handles are one sorted run and the Merger's
+ * merge passes run unchanged; the bytes every key shares are found PER SEGMENT on the device (one
+ * thread per segment) and the 8-byte prefix of a handle is taken after them.  The workspace
+ * (device, 256-byte aligned, no fill needed, one call at a time) is the Merger's plus 12 B per
+ * segment; its planned mark is derived from the record, source and segment counts and differs from
+ * the Merger's and the Sorter's.  The plan is synchronous, the emits asynchronous. */
+#define MTBLX_MERGE_MAX_SEGMENTS (1u << 24)
+#define MTBLX_MERGE_BADSEG 4u     /* totals[5]: a seg_off array is not 0 = off[0] <= ... <= off[nseg] = n */
+size_t mtblx_merge_seg_workspace_bytes(uint64_t nrec, uint32_t nsrc, uint32_t nseg);
+int mtblx_merge_seg_plan(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc, uint32_t nseg,
+                         uint64_t* totals, uint64_t* seg_end, void* workspace, size_t ws_bytes, void* stream);
+int mtblx_merge_seg_emit(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc, uint32_t nseg,
+                         int mode, const mtblx_merged* out, const void* workspace, size_t ws_bytes, void* stream);
+int mtblx_merge_seg_emit_reduce(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
+                                uint32_t nseg, const mtblx_reduce* spec, const mtblx_merged* out, void* workspace,
+                                size_t ws_bytes, void* stream);
+/* diagnostic (scripts/merger_scan_bench.py): mtblx_merge_seg_plan, plus the HIP-event time in ms of
+ * its phases: phase_ms[0] the offsets' check, the per-segment skips and the handles, [1 .. passes]
+ * the merge passes (passes = ceil(log2 nsrc)), [passes + 1] the grouping and the segment ends.
+ * phase_cap >= passes + 2. */
+int mtblx_merge_seg_plan_timed(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
+                               uint32_t nseg, uint64_t* totals, uint64_t* seg_end, void* workspace, size_t ws_bytes,
+                               void* stream, float* phase_ms, uint32_t phase_cap);
+
 /* ---- snappy raw decompression on the device (f4) ----
  * Reader::block's decompression step for CompressionType::Snappy (src/reader.rs:166-170 ->
  * src/compression.rs:57-68, :116-119, snap::raw::Decoder::decompress_vec), for a batch of

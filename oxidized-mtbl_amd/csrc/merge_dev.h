@@ -1,6 +1,7 @@
-// merge_dev.h — what the device Merger (merge.hip) and the device Sorter (sort.hip) share: the
-// 16-byte handle, the total order on handles, the merge-path pass, the grouping scan, the gather
-// and the workspace layout (DESIGN.md §4 "The Merger", "The Sorter").
+// merge_dev.h — what the device Merger (merge.hip), the device Sorter (sort.hip) and the segmented
+// merge (merge_seg.hip) share: the 16-byte handle, the total order on handles, the merge-path pass,
+// the grouping scan, the gather and the workspace layout (DESIGN.md §4 "The Merger", "The Sorter",
+// "Merged batched scans").
 //
 //   k_merge_pass    run 2j merged with run 2j+1, an unpaired run carried over.  A workgroup owns
 //                   kTile consecutive output handles; for every pair of runs its slice touches it
@@ -19,8 +20,9 @@
 // Order: keys compare as unsigned bytes then by length (Vec<u8>::cmp); equal keys by source number,
 // then by record index.  The order is total, so no pass ever reorders equal keys: run 2j holds
 // lower (source, index) pairs than run 2j+1.  Every pass is its own launch: no workgroup waits for
-// another.  Everything here sits in an unnamed namespace: each of the two translation units gets
-// its own copy, as with bounds.h.
+// another.  Everything here sits in an unnamed namespace: each of the translation units gets
+// its own copy, as with bounds.h.  The passes take their order as a policy (KeyOrder below; the
+// segmented merge orders by segment first).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,7 +47,9 @@ constexpr uint64_t kMagic = 0x4d54424c584d5247ull;
 constexpr uint64_t kSortMagic = 0x5354424c58535254ull;
 
 // workspace header words (u64)
-enum { H_GROUPS = 0, H_KEYB, H_NVAL, H_VALB, H_DROPPED, H_FLAGS, H_SKIP, H_PLANNED, H_FIRSTB, H_LASTB, H_WORDS = 32 };
+enum { H_GROUPS = 0, H_KEYB, H_NVAL, H_VALB, H_DROPPED, H_FLAGS, H_SKIP, H_PLANNED, H_FIRSTB, H_LASTB,
+       H_SEGSKIP,   // merge_seg.hip: u64 words from the header to the per-segment skip array
+       H_WORDS = 32 };
 constexpr int kReduceEdgeWords = 18;   // u64 words per tile of the device merge functions' edge array (reduce_dev.h)
 constexpr int kChan = 6;   // groups, key bytes, values, value bytes, first-value bytes, last-value bytes
 
@@ -113,6 +117,17 @@ __device__ __forceinline__ bool h_less(const SrcTab& t, Handle a, Handle b, uint
   return a.idx < b.idx;
 }
 
+// The order a pass merges by, as a policy: ctx() reads what the order needs from the workspace
+// header once per kernel, less() is the total order.  KeyOrder is the one above (the Merger, the
+// Sorter); merge_seg.hip brings its own (segment, key, source).
+struct KeyOrder {
+  typedef uint64_t Ctx;   // the shared key bytes
+  static __device__ __forceinline__ Ctx ctx(const uint64_t* hdr) { return hdr[H_SKIP]; }
+  static __device__ __forceinline__ bool less(const SrcTab& t, Handle a, Handle b, Ctx skip) {
+    return h_less(t, a, b, skip);
+  }
+};
+
 // Where the sorted runs of a pass lie.  start(): handles before run j of a level; count(): the
 // runs of level 0.
 struct SrcRuns {   // the merge: run j = sources [j << level, (j + 1) << level)
@@ -137,8 +152,9 @@ struct TileRuns {   // the sort: run j = handles [j * (kSortTile << level), (j +
 // below the answer and for none from it on, so each step probes 64 evenly spaced mids at once and
 // a ballot keeps the one interval where the answer lies: ceil(log64) dependent global loads where a
 // two-way search by one lane makes log2 of them (the chain every slice waits for before it stages)
+template <class Ord = KeyOrder>
 __device__ __forceinline__ uint32_t merge_path(const SrcTab& t, const Handle* a, uint32_t na, const Handle* b,
-                                               uint32_t nb, uint32_t d, uint64_t skip) {
+                                               uint32_t nb, uint32_t d, typename Ord::Ctx skip) {
   uint32_t lo = d > nb ? d - nb : 0, hi = d < na ? d : na;   // the answer is in [lo, hi]
   const uint32_t lane = threadIdx.x & 63u;
   while (lo < hi) {
@@ -148,7 +164,7 @@ __device__ __forceinline__ uint32_t merge_path(const SrcTab& t, const Handle* a,
     if (mid < hi) {
       MTBLX_CHK(a + mid, 16);
       MTBLX_CHK(b + (d - 1 - mid), 16);
-      below = h_less(t, a[mid], b[d - 1 - mid], skip);
+      below = Ord::less(t, a[mid], b[d - 1 - mid], skip);
     }
     const uint32_t c = (uint32_t)__popcll(__ballot(below));   // the probes below the answer: the first c
     const uint64_t next = (uint64_t)lo + (uint64_t)c * step;  // probe c, the first not below (if it exists)
@@ -158,13 +174,13 @@ __device__ __forceinline__ uint32_t merge_path(const SrcTab& t, const Handle* a,
   return lo;
 }
 
-template <class Runs>
+template <class Runs, class Ord = KeyOrder>
 __global__ void __launch_bounds__(kThreads) k_merge_pass(SrcTab t, uint64_t* hdr, const Handle* in, Handle* out,
                                                          uint32_t n, uint32_t level) {
   __shared__ Handle sin[kTile];
   __shared__ Handle sout[kTile];
   __shared__ uint32_t part[2];
-  const uint64_t skip = hdr[H_SKIP];
+  const typename Ord::Ctx skip = Ord::ctx(hdr);
   const uint64_t lo = (uint64_t)blockIdx.x * kTile;
   const uint64_t hi = lo + kTile < n ? lo + kTile : n;
   const uint32_t npair = (uint32_t)(((uint64_t)Runs::count(t, n) + (2ull << level) - 1) >> (level + 1));
@@ -183,7 +199,7 @@ __global__ void __launch_bounds__(kThreads) k_merge_pass(SrcTab t, uint64_t* hdr
     const uint32_t cnt = d1 - d0;
     const uint32_t wave = threadIdx.x >> 6;
     if (wave < 2) {   // wave 0: the slice's first diagonal, wave 1: its last
-      const uint32_t r = merge_path(t, in + ps, na, in + pm, nb, wave ? d1 : d0, skip);
+      const uint32_t r = merge_path<Ord>(t, in + ps, na, in + pm, nb, wave ? d1 : d0, skip);
       if ((threadIdx.x & 63u) == 0) part[wave] = r;
     }
     __syncthreads();
@@ -207,7 +223,7 @@ __global__ void __launch_bounds__(kThreads) k_merge_pass(SrcTab t, uint64_t* hdr
         const uint32_t first = l;
         while (l < r) {
           const uint32_t mid = l + (r - l) / 2;
-          if (h_less(t, sin[mid], h, skip)) l = mid + 1; else r = mid;
+          if (Ord::less(t, sin[mid], h, skip)) l = mid + 1; else r = mid;
         }
         sout[(isa ? k : k - ca) + (l - first)] = h;
       }

@@ -234,6 +234,80 @@ extern "C" int mtblx_sort_emit_reduce(const mtblx_records* in, const mtblx_reduc
   return mtblx_sort_impl_emit_reduce(in, spec, out, ws, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- segmented merge (csrc/merge_seg.hip): the argument checks need no device ----
+extern "C" size_t mtblx_merge_seg_impl_ws_bytes(uint64_t nrec, uint32_t nseg);
+extern "C" int mtblx_merge_seg_impl_plan(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
+                                         uint32_t nseg, uint64_t* totals, uint64_t* seg_end, void* ws, hipStream_t s,
+                                         float* phase_ms, uint32_t phase_cap);
+extern "C" int mtblx_merge_seg_impl_emit(const mtblx_records* src, uint32_t nsrc, uint32_t nseg, int mode,
+                                         const mtblx_reduce* spec, const mtblx_merged* out, void* ws, hipStream_t s);
+
+extern "C" size_t mtblx_merge_seg_workspace_bytes(uint64_t nrec, uint32_t nsrc, uint32_t nseg) {
+  (void)nsrc;   // the source and offset tables travel in the kernel arguments
+  if (nrec >= MTBLX_MERGE_MAX_RECORDS || nseg > MTBLX_MERGE_MAX_SEGMENTS) return 0;
+  return mtblx_merge_seg_impl_ws_bytes(nrec, nseg);
+}
+
+static int merge_seg_check(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc, uint32_t nseg,
+                           const void* ws, size_t wsb) {
+  if (nsrc > MTBLX_MERGE_MAX_SOURCES || nseg > MTBLX_MERGE_MAX_SEGMENTS) return MTBLX_E_INVAL;
+  if (nsrc && (!src || !seg_off)) return MTBLX_E_INVAL;
+  if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0) return MTBLX_E_INVAL;
+  uint64_t n = 0;
+  for (uint32_t i = 0; i < nsrc; ++i) {
+    if (!seg_off[i] || src[i].n >= MTBLX_MERGE_MAX_RECORDS) return MTBLX_E_INVAL;
+    if (src[i].n && (!src[i].key_end || !src[i].val_end)) return MTBLX_E_INVAL;
+    n += src[i].n;
+  }
+  if (n >= MTBLX_MERGE_MAX_RECORDS || wsb < mtblx_merge_seg_impl_ws_bytes(n, nseg)) return MTBLX_E_INVAL;
+  return MTBLX_OK;
+}
+
+extern "C" int mtblx_merge_seg_plan_timed(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
+                                          uint32_t nseg, uint64_t* totals, uint64_t* seg_end, void* ws, size_t wsb,
+                                          void* stream, float* phase_ms, uint32_t phase_cap) {
+  if (!totals || !phase_ms || (nseg && !seg_end)) return MTBLX_E_INVAL;
+  const int c = merge_seg_check(src, seg_off, nsrc, nseg, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_merge_seg_impl_plan(src, seg_off, nsrc, nseg, totals, seg_end, ws, reinterpret_cast<hipStream_t>(stream),
+                                   phase_ms, phase_cap);
+}
+
+extern "C" int mtblx_merge_seg_plan(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
+                                    uint32_t nseg, uint64_t* totals, uint64_t* seg_end, void* ws, size_t wsb,
+                                    void* stream) {
+  if (!totals || (nseg && !seg_end)) return MTBLX_E_INVAL;
+  const int c = merge_seg_check(src, seg_off, nsrc, nseg, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_merge_seg_impl_plan(src, seg_off, nsrc, nseg, totals, seg_end, ws, reinterpret_cast<hipStream_t>(stream),
+                                   nullptr, 0);
+}
+
+extern "C" int mtblx_merge_seg_emit(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
+                                    uint32_t nseg, int mode, const mtblx_merged* out, const void* ws, size_t wsb,
+                                    void* stream) {
+  if (!out || !out->flags || mode < MTBLX_MERGE_GROUPS || mode > MTBLX_MERGE_LAST) return MTBLX_E_INVAL;
+  if ((!out->keys && out->keys_cap) || (!out->key_end && out->key_end_cap) || (!out->vals && out->vals_cap) ||
+      (!out->val_end && out->val_end_cap) || (!out->grp_end && out->grp_end_cap))
+    return MTBLX_E_INVAL;
+  const int c = merge_seg_check(src, seg_off, nsrc, nseg, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  // the plain emit only reads the workspace
+  return mtblx_merge_seg_impl_emit(src, nsrc, nseg, mode, nullptr, out, const_cast<void*>(ws),
+                                   reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mtblx_merge_seg_emit_reduce(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
+                                           uint32_t nseg, const mtblx_reduce* spec, const mtblx_merged* out, void* ws,
+                                           size_t wsb, void* stream) {
+  int c = reduce_check(spec, out);
+  if (c != MTBLX_OK) return c;
+  c = merge_seg_check(src, seg_off, nsrc, nseg, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_merge_seg_impl_emit(src, nsrc, nseg, MTBLX_MERGE_FIRST, spec, out, ws,
+                                   reinterpret_cast<hipStream_t>(stream));
+}
+
 // ---- batched scans (csrc/scan.hip): the argument checks need no device ----
 extern "C" size_t mtblx_scan_impl_ws_bytes(uint32_t nq);
 extern "C" int mtblx_scan_impl_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,

@@ -5,7 +5,8 @@ Package layout
   codec.py    device batch decode (HIP kernels in csrc/decode.hip)
   writer.py   Writer / WriterBuilder mirror of src/writer.rs
   synth.py    deterministic synthetic workloads of BASELINE.json's configs
-  merger.py   Merger / MergerBuilder mirror of src/merger.rs over the device merge (csrc/merge.hip)
+  merger.py   Merger / MergerBuilder mirror of src/merger.rs over the device merge (csrc/merge.hip);
+              Merger.scan_batch / get_batch: batched reads of the merged view (csrc/merge_seg.hip)
   sorter.py   Sorter / SorterBuilder mirror of src/sorter.rs over the device sort (csrc/sort.hip)
   reduce.py   Reduce / MergeError: u64 sum / min / max merge functions evaluated on the device (csrc/reduce_dev.h)
 """
@@ -15,7 +16,7 @@ from .writer import CompressionType, OutOfOrderKey, Writer, WriterBuilder  # noq
 
 
 def __getattr__(name):   # Merger / MergerBuilder / Sorter / SorterBuilder need torch: imported on first use
-    if name in ("Merger", "MergerBuilder"):
+    if name in ("Merger", "MergerBuilder", "MergedScanBatch", "merge_segments"):
         from . import merger
         return getattr(merger, name)
     if name in ("Sorter", "SorterBuilder"):
@@ -25,4 +26,5 @@ def __getattr__(name):   # Merger / MergerBuilder / Sorter / SorterBuilder need 
 
 
 __all__ = ["Writer", "WriterBuilder", "CompressionType", "OutOfOrderKey", "Merger", "MergerBuilder", "Sorter", "SorterBuilder",
+           "MergedScanBatch", "merge_segments",
            "Reduce", "MergeError", "lib", "LIB_PATH", "EXPORTS"]

@@ -45,6 +45,8 @@ EXPORTS = [
     "mtblx_merge_workspace_bytes", "mtblx_merge_plan", "mtblx_merge_emit", "mtblx_merge_plan_timed",
     "mtblx_sort_workspace_bytes", "mtblx_sort_plan", "mtblx_sort_emit", "mtblx_sort_plan_timed",
     "mtblx_merge_emit_reduce", "mtblx_sort_emit_reduce",
+    "mtblx_merge_seg_workspace_bytes", "mtblx_merge_seg_plan", "mtblx_merge_seg_emit", "mtblx_merge_seg_emit_reduce",
+    "mtblx_merge_seg_plan_timed",
     "mtblx_snappy_compress_workspace_bytes", "mtblx_snappy_slots", "mtblx_snappy_compress_dev", "mtblx_frame_blocks",
     "mtblx_encode_index_c",
     "mtblx_scan_workspace_bytes", "mtblx_scan_plan", "mtblx_scan_emit",
@@ -56,6 +58,8 @@ MERGE_GROUPS, MERGE_CONCAT, MERGE_FIRST, MERGE_LAST = range(4)
 MERGE_UNSORTED, MERGE_INTERNAL = 1, 2          # totals[5] of mtblx_merge_plan
 MERGE_OVERFLOW, MERGE_NOT_PLANNED = 1, 2       # *flags of mtblx_merge_emit
 MERGE_BADVALUE = 4                             # *flags of mtblx_merge_emit_reduce / mtblx_sort_emit_reduce
+MERGE_MAX_SEGMENTS = 1 << 24                   # MTBLX_MERGE_MAX_SEGMENTS: segments per mtblx_merge_seg_plan
+MERGE_BADSEG = 4                               # totals[5] of mtblx_merge_seg_plan: a bad seg_off array
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)  # mtblx_reduce.op
 REDUCE_MAX_FIELDS = 8
 SORT_TILE = 1024                               # MTBLX_SORT_TILE: handles per tile-sorted run of mtblx_sort_plan
@@ -319,6 +323,18 @@ def lib() -> C.CDLL:
         L.mtblx_sort_emit_reduce.argtypes = [C.POINTER(Records), C.POINTER(ReduceSpec), C.POINTER(Merged), C.c_void_p,
                                              C.c_size_t, C.c_void_p]
         L.mtblx_sort_emit_reduce.restype = C.c_int
+        _seg = [C.POINTER(Records), C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32]   # src, seg_off, nsrc, nseg
+        L.mtblx_merge_seg_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+        L.mtblx_merge_seg_workspace_bytes.restype = C.c_size_t
+        L.mtblx_merge_seg_plan.argtypes = _seg + [u64p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_merge_seg_plan.restype = C.c_int
+        L.mtblx_merge_seg_plan_timed.argtypes = L.mtblx_merge_seg_plan.argtypes + [C.POINTER(C.c_float), C.c_uint32]
+        L.mtblx_merge_seg_plan_timed.restype = C.c_int
+        L.mtblx_merge_seg_emit.argtypes = _seg + [C.c_int, C.POINTER(Merged), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_merge_seg_emit.restype = C.c_int
+        L.mtblx_merge_seg_emit_reduce.argtypes = _seg + [C.POINTER(ReduceSpec), C.POINTER(Merged), C.c_void_p,
+                                                         C.c_size_t, C.c_void_p]
+        L.mtblx_merge_seg_emit_reduce.restype = C.c_int
         L.mtblx_scan_workspace_bytes.argtypes = [C.c_uint32]
         L.mtblx_scan_workspace_bytes.restype = C.c_size_t
         _file = [C.c_void_p, C.c_uint64, C.c_uint32]                                    # file, file_len, version
