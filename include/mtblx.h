@@ -23,6 +23,11 @@
  *    between calls -- every scratch buffer is the caller's (the block cut's too, since ABI v3);
  *    the one process-wide datum is a per-device cache of what the hardware is (compute-unit
  *    counts, kernel occupancy: csrc/devinfo.h), filled on first use with relaxed atomics.
+ *  - streams: every launch, memset and copy of a call goes to `stream`, never to the null stream
+ *    unless `stream` is it; inputs must be ready in stream order on `stream`, outputs are valid in
+ *    stream order on it, and a call that returns a size or a flag to the host synchronises
+ *    `stream` alone.  Exceptions: mtblx_entry_offsets and mtblx_encode_index(_c) allocate and free
+ *    device memory themselves, which waits for the whole device ("Streams").
  *  - return value: MTBLX_OK or a negative MTBLX_E_* (argument / HIP launch errors).
  *    Per-block outcomes are reported in `status[]` (MTBLX_ST_*), never by aborting.
  */
@@ -530,6 +535,10 @@ int mtblx_encode_blocks_planned(const mtblx_records* rec, const uint64_t* blk_re
  * -- built by BlockBuilder with `restart_interval` and framed with CompressionType::None,
  * then the 512-byte footer (block_size clamped to >= 1024 as WriterBuilder::block_size).
  * nblk == 0 writes the empty file.  Synchronous (allocates its temporaries: once per file);
+ * every copy it makes, the footer's read-backs of blk_rec and the END offsets included, is
+ * queued on `stream`.  The two ends of the cut are checked before anything is launched:
+ * blk_rec[0] <= blk_rec[nblk] <= rec->n, else MTBLX_E_INVAL and nothing is written.  Only the
+ * ends: the entries in between must ascend, which the kernels trust as mtblx_encode_blocks does.
  * *file_len = bytes written.  Byte-identical to the crate's Writer for the same records. */
 int mtblx_encode_index(const mtblx_records* rec, const uint64_t* blk_rec, uint32_t nblk, uint64_t block_size,
                        uint32_t restart_interval, const uint8_t* data, uint64_t region_off, uint64_t data_bytes,

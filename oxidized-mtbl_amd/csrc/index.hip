@@ -178,6 +178,26 @@ extern "C" int mtblx_encode_index_c(const mtblx_records* rec, const uint64_t* bl
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (block_size < 1024) block_size = 1024;   // WriterBuilder::block_size clamp (src/writer.rs:43-46)
   if (data_bytes + 13 + 512 > file_cap) return MTBLX_E_INVAL;
+  // The footer's counts come from the caller's blk_rec / END offsets.  They are inputs, ready in
+  // stream order on s, so they are read back on s (never on the null stream), and before the
+  // first launch: a cut whose two ENDS lie outside the records is refused before any kernel or
+  // copy reads the records through it.  The entries in between are the caller's to keep ascending.
+  uint64_t r0 = 0, r1 = 0, k0 = 0, k1 = 0, v0 = 0, v1 = 0;
+  if (nblk) {
+    if (hipMemcpyAsync(&r0, blk_rec, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(&r1, blk_rec + nblk, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      return MTBLX_E_HIP;
+    if (r0 > r1 || r1 > rec->n) return MTBLX_E_INVAL;
+    if (r0 && (hipMemcpyAsync(&k0, rec->key_end + r0 - 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+               hipMemcpyAsync(&v0, rec->val_end + r0 - 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess))
+      return MTBLX_E_HIP;
+    if (r1 && (hipMemcpyAsync(&k1, rec->key_end + r1 - 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+               hipMemcpyAsync(&v1, rec->val_end + r1 - 1, 8, hipMemcpyDeviceToHost, s) != hipSuccess))
+      return MTBLX_E_HIP;
+    // the destinations are locals: complete before any later return can leave this frame
+    if ((r0 || r1) && hipStreamSynchronize(s) != hipSuccess) return MTBLX_E_HIP;
+  }
   if (nblk && file != data + region_off &&
       hipMemcpyAsync(file, data + region_off, data_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
     return MTBLX_E_HIP;
@@ -224,17 +244,6 @@ extern "C" int mtblx_encode_index_c(const mtblx_records* rec, const uint64_t* bl
   if (ist != MTBLX_ST_OK || (h[3] & 1ull)) return ist == MTBLX_ST_OVERFLOW ? MTBLX_E_INVAL : MTBLX_E_FORMAT;
   const uint64_t idx_bytes = h[2];
   // Metadata::write_to_bytes (src/metadata.rs:61-79): 9 x u64 LE, zero pad, magic u32 LE at 508
-  uint64_t r0 = 0, r1 = 0, k0 = 0, k1 = 0, v0 = 0, v1 = 0;
-  if (nblk) {
-    if (hipMemcpy(&r0, blk_rec, 8, hipMemcpyDeviceToHost) || hipMemcpy(&r1, blk_rec + nblk, 8, hipMemcpyDeviceToHost))
-      return MTBLX_E_HIP;
-    if (r0 && (hipMemcpy(&k0, rec->key_end + r0 - 1, 8, hipMemcpyDeviceToHost) ||
-               hipMemcpy(&v0, rec->val_end + r0 - 1, 8, hipMemcpyDeviceToHost)))
-      return MTBLX_E_HIP;
-    if (r1 && (hipMemcpy(&k1, rec->key_end + r1 - 1, 8, hipMemcpyDeviceToHost) ||
-               hipMemcpy(&v1, rec->val_end + r1 - 1, 8, hipMemcpyDeviceToHost)))
-      return MTBLX_E_HIP;
-  }
   uint8_t foot[512];
   memset(foot, 0, sizeof foot);
   const uint64_t meta[9] = {data_bytes, block_size, compression, r1 - r0, nblk, data_bytes, idx_bytes, k1 - k0, v1 - v0};

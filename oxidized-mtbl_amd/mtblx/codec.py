@@ -3,6 +3,13 @@
 PyTorch is plumbing only (device memory, streams); the decode runs in libmtblx.so's
 HIP kernels.  Replaces the reference's per-block ``Block::init`` + ``BlockIter`` scan
 (/root/reference/src/block.rs:16-238) with one batched device call.
+
+Streams ("Streams"): with S the `stream` a call is given, or the current
+stream when it is None, every launch, fill and copy of the call goes to S, every buffer a wrapper
+allocates is allocated and filled under torch.cuda.stream(S), every host read-back follows the
+kernel that wrote the bytes on S, and the call waits for no stream but S.  Inputs must be ready
+in stream order on S; results are valid in stream order on S, and the host-reading methods of the
+result objects (to_host, totals_host, ...) read on the stream that wrote them.
 """
 from __future__ import annotations
 
@@ -79,9 +86,19 @@ class DeviceBatch:
 class DecodedBlocks:
     """Device outputs in the layout of include/mtblx.h (mtblx_decoded)."""
 
-    def __init__(self, nblk: int, rec_cap: int, keys_cap: int, vals_cap: int, device="cuda", values: bool = True):
+    def __init__(self, nblk: int, rec_cap: int, keys_cap: int, vals_cap: int, device="cuda", values: bool = True,
+                 stream=None):
         """values=False (with vals_cap=0): no value buffer at all -- `vals` is NULL in the C
-        struct, as decode_positions_into allows."""
+        struct, as decode_positions_into allows.  The buffers are allocated and zero-filled on
+        `stream` (default: the current stream): the stream of the launches that will write them."""
+        if not values and vals_cap:
+            raise ValueError("values=False needs vals_cap=0")
+        # the stream that last wrote the buffers: the fills here, then every launch into them
+        self._stream = _stream_of(stream, device)
+        with torch.cuda.stream(self._stream):
+            self._alloc(nblk, rec_cap, keys_cap, vals_cap, device, values)
+
+    def _alloc(self, nblk, rec_cap, keys_cap, vals_cap, device, values):
         z = lambda n, dt: torch.zeros(max(int(n), 1), dtype=dt, device=device)  # noqa: E731
         self.nblk = nblk
         self.nrec = z(nblk, torch.int32)
@@ -92,8 +109,6 @@ class DecodedBlocks:
         self.key_end = z(rec_cap, torch.int32)
         self.val_end = z(rec_cap, torch.int32)
         self.keys = z(keys_cap, torch.uint8)
-        if not values and vals_cap:
-            raise ValueError("values=False needs vals_cap=0")
         self.vals = z(vals_cap, torch.uint8) if values else torch.empty(0, dtype=torch.uint8, device=device)
         self.totals = z(4, torch.int64)
         self.rec_cap, self.keys_cap, self.vals_cap = int(rec_cap), int(keys_cap), int(vals_cap)
@@ -110,14 +125,20 @@ class DecodedBlocks:
     # ---------------- host views ----------------
     def totals_host(self, check: bool = True):
         """(records, key bytes, value bytes, flags); raises LaunchTimeout if the launch that
-        wrote them timed out (check=False returns the raw flags)."""
-        t = self.totals.cpu().numpy().view(np.uint64)
+        wrote them timed out (check=False returns the raw flags).  Read on the stream of that
+        launch, so the caller need not synchronise anything."""
+        with torch.cuda.stream(self._stream):
+            t = self.totals.cpu().numpy().view(np.uint64)
         if check and int(t[3]) & FLAG_TIMEOUT:
             raise LaunchTimeout("mtblx decode launch: look-back timeout, outputs discarded (re-run)")
         return int(t[0]), int(t[1]), int(t[2]), int(t[3])
 
     def to_host(self) -> "HostDecoded":
         nr, kb, vb, flags = self.totals_host()
+        with torch.cuda.stream(self._stream):
+            return self._to_host(nr, kb, vb, flags)
+
+    def _to_host(self, nr, kb, vb, flags) -> "HostDecoded":
         return HostDecoded(
             nrec=self.nrec[: self.nblk].cpu().numpy().view(np.uint32),
             rec_base=self.rec_base[: self.nblk].cpu().numpy().view(np.uint64),
@@ -166,11 +187,14 @@ class WorkspaceBusy(RuntimeError):
 
 
 class Workspace:
-    def __init__(self, nblk: int, device="cuda"):
+    def __init__(self, nblk: int, device="cuda", stream=None):
         L = _lib.lib()
         self.nbytes = int(L.mtblx_decode_workspace_bytes(nblk))
-        # zero-filled once: the kernels keep it consistent from call to call (include/mtblx.h)
-        self.buf = torch.zeros(self.nbytes, dtype=torch.uint8, device=device)
+        # zero-filled once: the kernels keep it consistent from call to call (include/mtblx.h).
+        # The fill runs on `stream` (default: the current stream); a first launch on another
+        # stream must be ordered after it by the caller.
+        with torch.cuda.stream(_stream_of(stream, device)):
+            self.buf = torch.zeros(self.nbytes, dtype=torch.uint8, device=device)
         self._last = None   # (stream handle, event recorded after the last launch on this workspace)
 
     def _claim(self, stream) -> int:
@@ -183,15 +207,29 @@ class Workspace:
                                 f"one workspace serves one call at a time -- synchronise, or give each stream its own")
         return h
 
-    def _launched(self, stream, h: int) -> None:
+    def _launched(self, stream, h: int):
+        """-> the stream of the launch (the outputs' host reads follow it: DecodedBlocks._stream)"""
         ev = self._last[1] if self._last is not None else torch.cuda.Event()
-        ev.record(stream if stream is not None else torch.cuda.current_stream())
+        s = stream if stream is not None else torch.cuda.current_stream()
+        ev.record(s)
         self._last = (h, ev)
+        return s
 
 
 def _stream_handle(stream) -> int:
     s = stream if stream is not None else torch.cuda.current_stream()
     return int(s.cuda_stream)
+
+
+def _stream_of(stream, device=None):
+    """S of the stream contract: `stream`, or the stream that is current
+    on `device` now.  Wrappers resolve it once, work under torch.cuda.stream(S) and hand S on."""
+    if stream is not None:
+        return stream
+    dev = torch.device(device) if device is not None else None
+    if dev is not None and dev.type != "cuda":
+        return None   # host tensors: no stream (torch.cuda.stream(None) is a no-op)
+    return torch.cuda.current_stream(dev)
 
 
 def count_blocks(batch: DeviceBatch, out: DecodedBlocks, ws: Workspace, stream=None) -> None:
@@ -200,21 +238,22 @@ def count_blocks(batch: DeviceBatch, out: DecodedBlocks, ws: Workspace, stream=N
     h = ws._claim(stream)
     rc = L.mtblx_count_blocks(C.byref(b), C.byref(o), C.c_void_p(ws.buf.data_ptr()), ws.nbytes,
                               C.c_void_p(h))
-    ws._launched(stream, h)
+    out._stream = ws._launched(stream, h)
     if rc != 0:
         raise RuntimeError(f"mtblx_count_blocks failed: {rc}")
 
 
 def decode_into(batch: DeviceBatch, out: DecodedBlocks, ws: Workspace, stream=None) -> None:
     """Asynchronous decode on `stream` into preallocated outputs (the timed hot call).
-    The buffers must be ready on `stream` (allocate them under torch.cuda.stream(stream) or
-    synchronize first): the library orders nothing across streams."""
+    The buffers must be ready on `stream` (allocate them under torch.cuda.stream(stream), as
+    DecodedBlocks(..., stream=) and Workspace(..., stream=) do, or synchronize first): the
+    library orders nothing across streams ("Streams", C2)."""
     L = _require_device()
     b, o = batch.cstruct(), out.cstruct()
     h = ws._claim(stream)
     rc = L.mtblx_decode_blocks(C.byref(b), C.byref(o), C.c_void_p(ws.buf.data_ptr()), ws.nbytes,
                                C.c_void_p(h))
-    ws._launched(stream, h)
+    out._stream = ws._launched(stream, h)
     if rc != 0:
         raise RuntimeError(f"mtblx_decode_blocks failed: {rc}")
 
@@ -232,7 +271,7 @@ def decode_positions_into(batch: DeviceBatch, out: DecodedBlocks, val_pos: torch
     h = ws._claim(stream)
     rc = L.mtblx_decode_blocks_valpos(C.byref(b), C.byref(o), C.c_void_p(_u(val_pos)),
                                       C.c_void_p(ws.buf.data_ptr()), ws.nbytes, C.c_void_p(h))
-    ws._launched(stream, h)
+    out._stream = ws._launched(stream, h)
     if rc != 0:
         raise RuntimeError(f"mtblx_decode_blocks_valpos failed: {rc}")
 
@@ -241,16 +280,17 @@ def decode_positions(batch: DeviceBatch, stream=None):
     """Size exactly (count pass), allocate, decode positions -> (DecodedBlocks without a value
     buffer, val_pos int32 tensor [records]).  Synchronises for the sizes and for the flags."""
     _require_device()
-    ws = Workspace(batch.nblk)
-    probe = DecodedBlocks(batch.nblk, 0, 0, 0)
-    count_blocks(batch, probe, ws, stream)
-    torch.cuda.synchronize()
-    nr, kb, _, _ = probe.totals_host()
-    out = DecodedBlocks(batch.nblk, nr, kb, 0, device=batch.data.device, values=False)
-    val_pos = torch.zeros(max(nr, 1), dtype=torch.int32, device=batch.data.device)
-    decode_positions_into(batch, out, val_pos, ws, stream)
-    torch.cuda.synchronize()
-    flags = out.totals_host()[3]   # raises LaunchTimeout on bit 1
+    dev = batch.data.device
+    s = _stream_of(stream, dev)
+    with torch.cuda.stream(s):   # fills, launches and read-backs all on s
+        ws = Workspace(batch.nblk, dev)
+        probe = DecodedBlocks(batch.nblk, 0, 0, 0, device=dev)
+        count_blocks(batch, probe, ws, s)
+        nr, kb, _, _ = probe.totals_host()   # synchronises s
+        out = DecodedBlocks(batch.nblk, nr, kb, 0, device=dev, values=False)
+        val_pos = torch.zeros(max(nr, 1), dtype=torch.int32, device=dev)
+        decode_positions_into(batch, out, val_pos, ws, s)
+        flags = out.totals_host()[3]   # synchronises s; raises LaunchTimeout on bit 1
     if flags & FLAG_OVERFLOW:
         raise RuntimeError("mtblx_decode_blocks_valpos: outputs sized by the count pass overflowed")
     return out, val_pos[:nr]
@@ -271,7 +311,7 @@ def decode_verify_into(batch: DeviceBatch, out: DecodedBlocks, ws: Workspace, cr
     rc = L.mtblx_decode_blocks_verify(C.byref(b), C.byref(o), C.c_void_p(_u(crc)), C.c_void_p(_u(bad)),
                                       flags, C.c_void_p(ws.buf.data_ptr()), ws.nbytes,
                                       C.c_void_p(h))
-    ws._launched(stream, h)
+    out._stream = ws._launched(stream, h)
     if rc != 0:
         raise RuntimeError(f"mtblx_decode_blocks_verify failed: {rc}")
 
@@ -279,16 +319,18 @@ def decode_verify_into(batch: DeviceBatch, out: DecodedBlocks, ws: Workspace, cr
 def decode_verify(batch: DeviceBatch, framed: bool = True, stream=None, fused=False):
     """Size exactly, allocate, decode + checksum in one launch -> (DecodedBlocks, crc, bad)."""
     _require_device()
-    ws = Workspace(batch.nblk)
-    probe = DecodedBlocks(batch.nblk, 0, 0, 0)
-    count_blocks(batch, probe, ws, stream)
-    torch.cuda.synchronize()
-    nr, kb, vb, _ = probe.totals_host()
-    out = DecodedBlocks(batch.nblk, nr, kb, vb)
-    n = max(batch.nblk, 1)
-    crc = torch.zeros(n, dtype=torch.int32, device=batch.data.device)
-    bad = torch.zeros(n, dtype=torch.uint8, device=batch.data.device)
-    decode_verify_into(batch, out, ws, crc, bad, framed, stream, fused)
+    dev = batch.data.device
+    s = _stream_of(stream, dev)
+    with torch.cuda.stream(s):
+        ws = Workspace(batch.nblk, dev)
+        probe = DecodedBlocks(batch.nblk, 0, 0, 0, device=dev)
+        count_blocks(batch, probe, ws, s)
+        nr, kb, vb, _ = probe.totals_host()   # synchronises s
+        out = DecodedBlocks(batch.nblk, nr, kb, vb, device=dev)
+        n = max(batch.nblk, 1)
+        crc = torch.zeros(n, dtype=torch.int32, device=dev)
+        bad = torch.zeros(n, dtype=torch.uint8, device=dev)
+        decode_verify_into(batch, out, ws, crc, bad, framed, s, fused)
     return out, crc[: batch.nblk], bad[: batch.nblk]
 
 
@@ -299,21 +341,24 @@ def decode_counted(batch: DeviceBatch, out: DecodedBlocks, ws: Workspace, stream
     h = ws._claim(stream)
     rc = L.mtblx_decode_counted(C.byref(b), C.byref(o), C.c_void_p(ws.buf.data_ptr()), ws.nbytes,
                                 C.c_void_p(h))
-    ws._launched(stream, h)
+    out._stream = ws._launched(stream, h)
     if rc != 0:
         raise RuntimeError(f"mtblx_decode_counted failed: {rc}")
 
 
 def decode_blocks(batch: DeviceBatch, stream=None) -> DecodedBlocks:
-    """Size exactly (count pass), allocate, decode.  Synchronises once for the sizes."""
+    """Size exactly (count pass), allocate, decode.  Synchronises `stream` once for the sizes;
+    the decode itself is left running on it."""
     _require_device()
-    ws = Workspace(batch.nblk)
-    probe = DecodedBlocks(batch.nblk, 0, 0, 0)
-    count_blocks(batch, probe, ws, stream)
-    torch.cuda.synchronize()
-    nr, kb, vb, _ = probe.totals_host()
-    out = DecodedBlocks(batch.nblk, nr, kb, vb)
-    decode_into(batch, out, ws, stream)
+    dev = batch.data.device
+    s = _stream_of(stream, dev)
+    with torch.cuda.stream(s):   # the workspace goes back to the allocator as a block of s: reuse is in stream order
+        ws = Workspace(batch.nblk, dev)
+        probe = DecodedBlocks(batch.nblk, 0, 0, 0, device=dev)
+        count_blocks(batch, probe, ws, s)
+        nr, kb, vb, _ = probe.totals_host()   # synchronises s
+        out = DecodedBlocks(batch.nblk, nr, kb, vb, device=dev)
+        decode_into(batch, out, ws, s)
     return out
 
 
@@ -324,11 +369,13 @@ def crc32c_blocks(batch: DeviceBatch, framed: bool = False, stream=None):
     Reader::block's assert_eq panics (src/reader.rs:159-164)."""
     L = _require_device()
     n = max(batch.nblk, 1)
-    crc = torch.zeros(n, dtype=torch.int32, device=batch.data.device)
-    bad = torch.zeros(n, dtype=torch.uint8, device=batch.data.device) if framed else None
+    s = _stream_of(stream, batch.data.device)
+    with torch.cuda.stream(s):
+        crc = torch.zeros(n, dtype=torch.int32, device=batch.data.device)
+        bad = torch.zeros(n, dtype=torch.uint8, device=batch.data.device) if framed else None
     b = batch.cstruct()
     rc = L.mtblx_crc32c_blocks(C.byref(b), C.c_void_p(crc.data_ptr()), C.c_void_p(bad.data_ptr() if framed else 0),
-                               1 if framed else 0, C.c_void_p(_stream_handle(stream)))
+                               1 if framed else 0, C.c_void_p(_stream_handle(s)))
     if rc != 0:
         raise RuntimeError(f"mtblx_crc32c_blocks failed: {rc}")
     return crc[: batch.nblk], (bad[: batch.nblk] if framed else None)
@@ -396,15 +443,17 @@ def snappy_decompress(batch: SnappyBatch, stream=None):
     """Layout + decompress -> (DeviceBatch of the decompressed blocks, status int32 [nblk]).
     The DeviceBatch feeds decode_blocks directly (a failed block has length 0)."""
     _require_device()
-    lay = SnappyLayout(batch.nblk, batch.data.device)
-    snappy_dir(batch, lay, stream)
-    torch.cuda.synchronize()
-    t = lay.totals.cpu().numpy().view(np.uint64)
-    total, mx = int(t[0]), int(t[1])
-    dst = torch.zeros(max(total, 16), dtype=torch.uint8, device=batch.data.device)
-    status = torch.zeros(max(batch.nblk, 1), dtype=torch.int32, device=batch.data.device)
-    dec_len = torch.zeros(max(batch.nblk, 1), dtype=torch.int32, device=batch.data.device)
-    snappy_decompress_into(batch, lay, dst, status, dec_len, mx, stream)
+    dev = batch.data.device
+    s = _stream_of(stream, dev)
+    with torch.cuda.stream(s):
+        lay = SnappyLayout(batch.nblk, dev)
+        snappy_dir(batch, lay, s)
+        t = lay.totals.cpu().numpy().view(np.uint64)   # synchronises s
+        total, mx = int(t[0]), int(t[1])
+        dst = torch.zeros(max(total, 16), dtype=torch.uint8, device=dev)
+        status = torch.zeros(max(batch.nblk, 1), dtype=torch.int32, device=dev)
+        dec_len = torch.zeros(max(batch.nblk, 1), dtype=torch.int32, device=dev)
+        snappy_decompress_into(batch, lay, dst, status, dec_len, mx, s)
     out = DeviceBatch(dst, lay.dst_off[: batch.nblk], dec_len[: batch.nblk], mx)
     return out, status[: batch.nblk]
 
@@ -449,21 +498,17 @@ def snappy_compress(batch: DeviceBatch, stream=None):
     """Slots + compress -> (SnappyBatch of the compressed blocks, status int32 [nblk]): the
     block-level counterpart of snappy_decompress.  Each block becomes a Snappy raw stream in its
     own 16-byte aligned slot; status is MTBLX_ST_OK per block (slots sized here always fit).
-    Synchronises for the slots' size (and, with a `stream`, around its own buffer fills); the
-    compression itself is left running on `stream`."""
+    Synchronises `stream` for the slots' size; the compression itself is left running on it."""
     _require_device()
     dev = batch.data.device
-    slots = SnappySlots(batch.nblk, dev)
-    if stream is not None:   # the zero fills of a fresh buffer run on the current stream, the kernels on `stream`
-        torch.cuda.synchronize()
-    snappy_slots(batch, slots, stream)
-    torch.cuda.synchronize()
-    total = int(slots.totals[0].item())
-    dst = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
-    n = max(batch.nblk, 1)
-    dst_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    status = torch.zeros(n, dtype=torch.int32, device=dev)
-    if stream is not None:
-        torch.cuda.synchronize()
-    snappy_compress_into(batch, slots, dst, dst_len, status, stream)
+    s = _stream_of(stream, dev)
+    with torch.cuda.stream(s):   # the buffers' fills run on s, like the kernels that write them
+        slots = SnappySlots(batch.nblk, dev)
+        snappy_slots(batch, slots, s)
+        total = int(slots.totals[0].item())   # synchronises s
+        dst = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        n = max(batch.nblk, 1)
+        dst_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        status = torch.zeros(n, dtype=torch.int32, device=dev)
+        snappy_compress_into(batch, slots, dst, dst_len, status, s)
     return SnappyBatch(dst, slots.dst_off[: batch.nblk], dst_len[: batch.nblk]), status[: batch.nblk]

@@ -33,6 +33,7 @@ class DeviceRecords:
     key_end: torch.Tensor
     vals: torch.Tensor
     val_end: torch.Tensor
+    stream: object = None   # set by the calls that produce records: the stream their host reads go through
 
     @property
     def n(self) -> int:
@@ -43,7 +44,13 @@ class DeviceRecords:
         return Records(u(self.keys), u(self.key_end), u(self.vals), u(self.val_end), self.n)
 
     @staticmethod
-    def from_list(records, device="cuda") -> "DeviceRecords":
+    def from_list(records, device="cuda", stream=None) -> "DeviceRecords":
+        """upload on `stream` (default: the current stream)"""
+        if stream is not None:
+            with torch.cuda.stream(stream):
+                r = DeviceRecords.from_list(records, device)
+            r.stream = stream
+            return r
         import numpy as np
         ks = b"".join(bytes(k) for k, _ in records)
         vs = b"".join(bytes(v) for _, v in records)
@@ -82,33 +89,35 @@ def plan(recs: DeviceRecords, block_size: int = 8192, restart_interval: int = 16
     workspace that does not fit falls back to the serial walk's 16 B per shard)."""
     L = codec._require_device()
     dev = recs.key_end.device
-    if shard_rec is None:
-        shard_rec = torch.tensor([0, recs.n], dtype=torch.int64, device=dev)
-    nsh = int(shard_rec.numel()) - 1
-    if workspace is None:
-        try:
-            workspace = PlanWorkspace(recs.n, nsh, restart_interval, keep, device=dev)
-        except torch.OutOfMemoryError:
-            if keep:
-                raise
-            workspace = PlanWorkspace(recs.n, nsh, restart_interval, device=dev, serial=True)
-    rc_ = recs.cstruct()
-    nb = C.c_uint64(0)
-    fl = C.c_uint32(0)
-    st = C.c_void_p(codec._stream_handle(stream))
-    # one call: every block holds >= 1 record, so the shards' record count + 1 always suffices
-    cap = max(recs.n, 0) + 1
-    blk = torch.empty(cap, dtype=torch.int64, device=dev)
-    args = [C.byref(rc_), C.c_void_p(shard_rec.data_ptr()), nsh, int(block_size), int(restart_interval),
-            C.c_void_p(blk.data_ptr()), cap, C.byref(nb), C.byref(fl)]
-    ws = [C.c_void_p(workspace.ptr), workspace.nbytes]
-    kept = None
-    if keep:
-        kb = int(L.mtblx_plan_keep_bytes(recs.n))
-        kept = Plan(torch.empty(kb + 256, dtype=torch.uint8, device=dev), int(restart_interval))
-        rc = L.mtblx_encode_plan_keep(*args, C.c_void_p(kept.ptr), kb, *ws, st)
-    else:
-        rc = L.mtblx_encode_plan(*args, *ws, st)
+    s = codec._stream_of(stream, dev)
+    with torch.cuda.stream(s):   # the default workspace, shard_rec, blk and the kept plan are blocks of s
+        if shard_rec is None:
+            shard_rec = torch.tensor([0, recs.n], dtype=torch.int64, device=dev)
+        nsh = int(shard_rec.numel()) - 1
+        if workspace is None:
+            try:
+                workspace = PlanWorkspace(recs.n, nsh, restart_interval, keep, device=dev)
+            except torch.OutOfMemoryError:
+                if keep:
+                    raise
+                workspace = PlanWorkspace(recs.n, nsh, restart_interval, device=dev, serial=True)
+        rc_ = recs.cstruct()
+        nb = C.c_uint64(0)
+        fl = C.c_uint32(0)
+        st = C.c_void_p(int(s.cuda_stream))
+        # one call: every block holds >= 1 record, so the shards' record count + 1 always suffices
+        cap = max(recs.n, 0) + 1
+        blk = torch.empty(cap, dtype=torch.int64, device=dev)
+        args = [C.byref(rc_), C.c_void_p(shard_rec.data_ptr()), nsh, int(block_size), int(restart_interval),
+                C.c_void_p(blk.data_ptr()), cap, C.byref(nb), C.byref(fl)]
+        ws = [C.c_void_p(workspace.ptr), workspace.nbytes]
+        kept = None
+        if keep:
+            kb = int(L.mtblx_plan_keep_bytes(recs.n))
+            kept = Plan(torch.empty(kb + 256, dtype=torch.uint8, device=dev), int(restart_interval))
+            rc = L.mtblx_encode_plan_keep(*args, C.c_void_p(kept.ptr), kb, *ws, st)   # synchronises s: nb, fl
+        else:
+            rc = L.mtblx_encode_plan(*args, *ws, st)                                  # synchronises s: nb, fl
     if rc == _lib.MTBLX_E_FORMAT:
         raise WriterPanic(int(fl.value))
     if rc != 0:
@@ -137,34 +146,41 @@ class Encoded:
     blk_len: torch.Tensor   # int32 content lengths
     status: torch.Tensor    # int32 MTBLX_ST_*
     totals: torch.Tensor    # int64 [2]: bytes, flags
+    stream: object = None   # the stream of the encode launch: check() and batch() read on it
 
     def check(self) -> "Encoded":
         """raise codec.LaunchTimeout if the encode launch's look-back timed out (totals[1] bit 1)"""
-        if int(self.totals[1].item()) & codec.FLAG_TIMEOUT:
+        with torch.cuda.stream(self.stream):
+            flags = int(self.totals[1].item())
+        if flags & codec.FLAG_TIMEOUT:
             raise codec.LaunchTimeout("mtblx_encode_blocks: look-back timeout, outputs discarded (re-run)")
         return self
 
     def batch(self) -> codec.DeviceBatch:
         """the encoded blocks as a decode batch (mtblx_decode_blocks input)"""
-        ml = int(self.blk_len.max().item()) if self.blk_len.numel() else 0
+        with torch.cuda.stream(self.stream):
+            ml = int(self.blk_len.max().item()) if self.blk_len.numel() else 0
         return codec.DeviceBatch(self.out, self.blk_off, self.blk_len, ml)
 
 
 class EncodeBuffers:
     """Output + workspace of mtblx_encode_blocks, sized once for a record set and plan."""
 
-    def __init__(self, recs: DeviceRecords, nblk: int, device="cuda"):
+    def __init__(self, recs: DeviceRecords, nblk: int, device="cuda", stream=None):
+        """allocated (and `totals` zero-filled) on `stream`, default the current stream: the
+        stream encode_into will run on"""
         L = _lib.lib()
         n = recs.n
         cap = int(recs.keys.numel()) + int(recs.vals.numel()) + 19 * n + 30 * nblk + 64
-        self.out = torch.empty(cap, dtype=torch.uint8, device=device)
         m = max(nblk, 1)
-        self.blk_off = torch.empty(m, dtype=torch.int64, device=device)
-        self.blk_len = torch.empty(m, dtype=torch.int32, device=device)
-        self.status = torch.empty(m, dtype=torch.int32, device=device)
-        self.totals = torch.zeros(2, dtype=torch.int64, device=device)
-        self.ws_bytes = int(L.mtblx_encode_workspace_bytes(m))
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
+        with torch.cuda.stream(codec._stream_of(stream, device)):
+            self.out = torch.empty(cap, dtype=torch.uint8, device=device)
+            self.blk_off = torch.empty(m, dtype=torch.int64, device=device)
+            self.blk_len = torch.empty(m, dtype=torch.int32, device=device)
+            self.status = torch.empty(m, dtype=torch.int32, device=device)
+            self.totals = torch.zeros(2, dtype=torch.int64, device=device)
+            self.ws_bytes = int(L.mtblx_encode_workspace_bytes(m))
+            self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
         self.nblk = nblk
 
 
@@ -178,19 +194,22 @@ def encode_into(recs: DeviceRecords, blk_rec: torch.Tensor, bufs: EncodeBuffers,
             C.c_void_p(bufs.out.data_ptr()), bufs.out.numel(), C.c_void_p(bufs.blk_off.data_ptr()),
             C.c_void_p(bufs.blk_len.data_ptr()), C.c_void_p(bufs.status.data_ptr()), C.c_void_p(bufs.totals.data_ptr()),
             C.c_void_p(bufs.ws.data_ptr()), bufs.ws_bytes]
+    s = codec._stream_of(stream, bufs.out.device)
     if plan is not None:
-        rc = L.mtblx_encode_blocks_planned(*args, C.c_void_p(plan.ptr), C.c_void_p(codec._stream_handle(stream)))
+        rc = L.mtblx_encode_blocks_planned(*args, C.c_void_p(plan.ptr), C.c_void_p(int(s.cuda_stream)))
     else:
-        rc = L.mtblx_encode_blocks(*args, C.c_void_p(codec._stream_handle(stream)))
+        rc = L.mtblx_encode_blocks(*args, C.c_void_p(int(s.cuda_stream)))
     if rc != 0:
         raise RuntimeError(f"mtblx_encode_blocks failed: {rc}")
-    return Encoded(bufs.out, bufs.blk_off[:nblk], bufs.blk_len[:nblk], bufs.status[:nblk], bufs.totals)
+    return Encoded(bufs.out, bufs.blk_off[:nblk], bufs.blk_len[:nblk], bufs.status[:nblk], bufs.totals, s)
 
 
 def encode_blocks(recs: DeviceRecords, blk_rec: torch.Tensor, restart_interval: int = 16, framed: bool = True,
                   stream=None, plan: "Plan | None" = None) -> Encoded:
-    bufs = EncodeBuffers(recs, int(blk_rec.numel()) - 1, device=recs.key_end.device)
-    return encode_into(recs, blk_rec, bufs, restart_interval, framed, stream, plan)
+    dev = recs.key_end.device
+    s = codec._stream_of(stream, dev)
+    bufs = EncodeBuffers(recs, int(blk_rec.numel()) - 1, device=dev, stream=s)
+    return encode_into(recs, blk_rec, bufs, restart_interval, framed, s, plan)
 
 
 def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: int = 16, stream=None,
@@ -202,11 +221,21 @@ def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: in
     records.  Snappy: the blocks are built unframed, compressed on the device
     (mtblx_snappy_compress_dev) and framed as stored (mtblx_frame_blocks); every block
     decompresses to the None file's block, the compressed bytes themselves are this library's
-    (valid Snappy, not pinned to any other compressor's).  Other types are host-only."""
+    (valid Snappy, not pinned to any other compressor's).  Other types are host-only.
+    Everything runs on `stream` (default: the current stream), which the call synchronises for
+    the sizes it reads back; mtblx_encode_index_c allocates and frees device memory itself, which
+    waits for the whole device ("Streams", the exceptions to C6)."""
     compression = int(compression)
     if compression not in (CompressionType.None_, CompressionType.Snappy):
         raise ValueError(f"write_file: compression {compression} is not available on the device (None and Snappy "
                          f"are); for zlib and zstd use the host path, write_into(Writer(compression=...))")
+    s = codec._stream_of(stream, recs.key_end.device)
+    with torch.cuda.stream(s):   # every buffer, fill and read-back below is on s
+        return _write_file(recs, block_size, restart_interval, s, compression)
+
+
+def _write_file(recs: DeviceRecords, block_size: int, restart_interval: int, stream, compression: int) -> torch.Tensor:
+    """write_file's body; `stream` is the current stream"""
     L = codec._require_device()
     dev = recs.key_end.device
     kept = None
@@ -222,8 +251,7 @@ def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: in
     snappy = compression == CompressionType.Snappy
     if nblk:
         e = encode_blocks(recs, blk, restart_interval, framed=not snappy, stream=stream, plan=kept)
-        torch.cuda.synchronize()
-        e.check()
+        e.check()   # synchronises `stream`
         if int(e.totals[1].item()) & 1:
             raise WriterPanic(int((e.status != 0).nonzero()[0].item()) if bool((e.status != 0).any()) else 0)
         data_bytes = int(e.totals[0].item())
@@ -235,8 +263,7 @@ def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: in
     tail = kbytes + 36 * nblk + 64 + 512
     if snappy and nblk:
         comp, cst = codec.snappy_compress(e.batch(), stream=stream)
-        torch.cuda.synchronize()   # the kernels ran on `stream`; the reads below are on the current stream
-        stored = int(comp.src_len.sum().item())   # synchronises: the compressed sizes size the file
+        stored = int(comp.src_len.sum().item())   # synchronises `stream`: the compressed sizes size the file
         if bool((cst != 0).any()):
             raise RuntimeError("mtblx_snappy_compress_dev: a block did not fit its slot")
         del e, data   # the raw contents are not needed any more
@@ -244,7 +271,6 @@ def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: in
         file = torch.empty(cap, dtype=torch.uint8, device=dev)
         off = torch.empty(nblk, dtype=torch.int64, device=dev)
         ftot = torch.zeros(2, dtype=torch.int64, device=dev)
-        torch.cuda.synchronize()   # ftot's fill (current stream) before k_len_scan writes it on `stream`
         wsb = int(L.mtblx_snappy_compress_workspace_bytes(nblk))
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         u = codec._u
@@ -254,8 +280,7 @@ def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: in
                                   C.c_void_p(codec._stream_handle(stream)))
         if rc != 0:
             raise RuntimeError(f"mtblx_frame_blocks failed: {rc}")
-        torch.cuda.synchronize()
-        data_bytes, fflags = (int(x) for x in ftot.tolist())
+        data_bytes, fflags = (int(x) for x in ftot.tolist())   # synchronises `stream`
         if fflags & 1:
             raise RuntimeError("mtblx_frame_blocks: the framed blocks did not fit")
         data, ln = file, comp.src_len

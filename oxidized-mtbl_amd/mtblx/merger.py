@@ -59,10 +59,12 @@ class Grouped:
     vals: torch.Tensor
     val_end: torch.Tensor
     grp_end: torch.Tensor
+    stream: object = None   # the stream the tensors were produced on: to_list() reads on it
 
     def to_list(self):
-        ke, ve, ge = (t.cpu().numpy() for t in (self.key_end, self.val_end, self.grp_end))
-        k, v = self.keys.cpu().numpy().tobytes(), self.vals.cpu().numpy().tobytes()
+        with torch.cuda.stream(self.stream):
+            ke, ve, ge = (t.cpu().numpy() for t in (self.key_end, self.val_end, self.grp_end))
+            k, v = self.keys.cpu().numpy().tobytes(), self.vals.cpu().numpy().tobytes()
         out, pk, pv, pg = [], 0, 0, 0
         for g in range(ke.size):
             vs = []
@@ -75,8 +77,9 @@ class Grouped:
 
 
 def _records_list(r: DeviceRecords):
-    ke, ve = r.key_end.cpu().numpy(), r.val_end.cpu().numpy()
-    k, v = r.keys.cpu().numpy().tobytes(), r.vals.cpu().numpy().tobytes()
+    with torch.cuda.stream(r.stream):   # the stream that produced them (None: the current one)
+        ke, ve = r.key_end.cpu().numpy(), r.val_end.cpu().numpy()
+        k, v = r.keys.cpu().numpy().tobytes(), r.vals.cpu().numpy().tobytes()
     out, pk, pv = [], 0, 0
     for i in range(ke.size):
         out.append((k[pk: ke[i]], v[pv: ve[i]]))
@@ -143,26 +146,28 @@ def merge_records(sources, mode, stream=None, device=None):
         if m in (_lib.MERGE_FIRST, _lib.MERGE_LAST) and groups:   # vals was sized by its upper bound
             vals = vals[: int(val_end[-1].item())]
     if grouped:
-        return Grouped(keys, key_end, vals, val_end, grp_end)
-    return DeviceRecords(keys, key_end, vals, val_end)
+        return Grouped(keys, key_end, vals, val_end, grp_end, s)
+    return DeviceRecords(keys, key_end, vals, val_end, s)
 
 
 def _regroup(parts, stream):
     """Grouped results of consecutive source chunks -> the Grouped of all their sources: the value
     bytes of every key joined chunk by chunk (CONCAT over the groups' byte ranges), and the value
-    lengths joined the same way (CONCAT over each group's lengths as 8-byte words)."""
+    lengths joined the same way (CONCAT over each group's lengths as 8-byte words).  `stream`
+    is the stream the parts were produced on; the torch ops between the merges run on it too."""
     a, b = [], []
-    for p in parts:
-        nv = int(p.val_end.numel())
-        ng = int(p.grp_end.numel())
-        gbytes = p.val_end[p.grp_end - 1] if ng else p.grp_end
-        a.append(DeviceRecords(p.keys, p.key_end, p.vals, gbytes))
-        lens = torch.diff(p.val_end, prepend=p.val_end.new_zeros(1)) if nv else p.val_end
-        b.append(DeviceRecords(p.keys, p.key_end, lens.contiguous().view(torch.uint8), p.grp_end * 8))
-    va = merge_records(a, "concat", stream)
-    vb = merge_records(b, "concat", stream)
-    lens = vb.vals.view(torch.int64) if vb.vals.numel() else vb.val_end.new_zeros(0)
-    return Grouped(va.keys, va.key_end, va.vals, torch.cumsum(lens, 0), vb.val_end // 8)
+    with torch.cuda.stream(stream):
+        for p in parts:
+            nv = int(p.val_end.numel())
+            ng = int(p.grp_end.numel())
+            gbytes = p.val_end[p.grp_end - 1] if ng else p.grp_end
+            a.append(DeviceRecords(p.keys, p.key_end, p.vals, gbytes))
+            lens = torch.diff(p.val_end, prepend=p.val_end.new_zeros(1)) if nv else p.val_end
+            b.append(DeviceRecords(p.keys, p.key_end, lens.contiguous().view(torch.uint8), p.grp_end * 8))
+        va = merge_records(a, "concat", stream)
+        vb = merge_records(b, "concat", stream)
+        lens = vb.vals.view(torch.int64) if vb.vals.numel() else vb.val_end.new_zeros(0)
+        return Grouped(va.keys, va.key_end, va.vals, torch.cumsum(lens, 0), vb.val_end // 8, stream)
 
 
 def merge_all(sources, mode, stream=None, device=None):
@@ -172,6 +177,8 @@ def merge_all(sources, mode, stream=None, device=None):
     sources = list(sources)
     grouped = mode == "groups"
     first = True
+    dev = torch.device(device) if device is not None else (sources[0].key_end.device if sources else None)
+    stream = codec._stream_of(stream, dev)   # resolved once: every round runs on the same stream
     while first or len(sources) > 1:
         chunks = [sources[i: i + _lib.MERGE_MAX_SOURCES] for i in range(0, len(sources), _lib.MERGE_MAX_SOURCES)] \
             or [[]]
@@ -240,8 +247,8 @@ def _merge_segments_64(sources, seg_offs, nseg, mode, s, dev):
         if m in (_lib.MERGE_FIRST, _lib.MERGE_LAST) and groups:   # vals was sized by its upper bound
             vals = vals[: int(val_end[-1].item())]
     if grouped:
-        return Grouped(keys, key_end, vals, val_end, grp_end), seg_end
-    return DeviceRecords(keys, key_end, vals, val_end), seg_end
+        return Grouped(keys, key_end, vals, val_end, grp_end, s), seg_end
+    return DeviceRecords(keys, key_end, vals, val_end, s), seg_end
 
 
 def _seg_off_of(seg_end):
@@ -251,18 +258,19 @@ def _seg_off_of(seg_end):
 def _regroup_segments(parts, seg_ends, nseg, s, dev):
     """_regroup for segmented results: the two CONCATs are segmented merges over the rounds' groups"""
     a, b, offs = [], [], []
-    for p, se in zip(parts, seg_ends):
-        nv = int(p.val_end.numel())
-        ng = int(p.grp_end.numel())
-        gbytes = p.val_end[p.grp_end - 1] if ng else p.grp_end
-        a.append(DeviceRecords(p.keys, p.key_end, p.vals, gbytes))
-        lens = torch.diff(p.val_end, prepend=p.val_end.new_zeros(1)) if nv else p.val_end
-        b.append(DeviceRecords(p.keys, p.key_end, lens.contiguous().view(torch.uint8), p.grp_end * 8))
-        offs.append(_seg_off_of(se))
-    va, se = _merge_segments_64(a, offs, nseg, "concat", s, dev)
-    vb, _ = _merge_segments_64(b, offs, nseg, "concat", s, dev)
-    lens = vb.vals.view(torch.int64) if vb.vals.numel() else vb.val_end.new_zeros(0)
-    return Grouped(va.keys, va.key_end, va.vals, torch.cumsum(lens, 0), vb.val_end // 8), se
+    with torch.cuda.stream(s):
+        for p, se in zip(parts, seg_ends):
+            nv = int(p.val_end.numel())
+            ng = int(p.grp_end.numel())
+            gbytes = p.val_end[p.grp_end - 1] if ng else p.grp_end
+            a.append(DeviceRecords(p.keys, p.key_end, p.vals, gbytes))
+            lens = torch.diff(p.val_end, prepend=p.val_end.new_zeros(1)) if nv else p.val_end
+            b.append(DeviceRecords(p.keys, p.key_end, lens.contiguous().view(torch.uint8), p.grp_end * 8))
+            offs.append(_seg_off_of(se))
+        va, se = _merge_segments_64(a, offs, nseg, "concat", s, dev)
+        vb, _ = _merge_segments_64(b, offs, nseg, "concat", s, dev)
+        lens = vb.vals.view(torch.int64) if vb.vals.numel() else vb.val_end.new_zeros(0)
+        return Grouped(va.keys, va.key_end, va.vals, torch.cumsum(lens, 0), vb.val_end // 8, s), se
 
 
 def merge_segments(sources, seg_offs, mode, stream=None, device=None):
@@ -286,18 +294,19 @@ def merge_segments(sources, seg_offs, mode, stream=None, device=None):
     s = stream if stream is not None else torch.cuda.current_stream(dev)
     grouped = mode == "groups"
     first = True
-    while first or len(sources) > 1:
-        idx = list(range(0, len(sources), _lib.MERGE_MAX_SOURCES)) or [0]
-        outs = []
-        for i in idx:
-            c, o = sources[i: i + _lib.MERGE_MAX_SOURCES], seg_offs[i: i + _lib.MERGE_MAX_SOURCES]
-            if grouped and not first:
-                outs.append(_regroup_segments(c, [x[1:] for x in o], nseg, s, dev))
-            else:
-                outs.append(_merge_segments_64(c, o, nseg, mode, s, dev))
-        sources = [r for r, _ in outs]
-        seg_offs = [_seg_off_of(se) for _, se in outs]
-        first = False
+    with torch.cuda.stream(s):   # the seg_off joins between the rounds run on s, like the rounds
+        while first or len(sources) > 1:
+            idx = list(range(0, len(sources), _lib.MERGE_MAX_SOURCES)) or [0]
+            outs = []
+            for i in idx:
+                c, o = sources[i: i + _lib.MERGE_MAX_SOURCES], seg_offs[i: i + _lib.MERGE_MAX_SOURCES]
+                if grouped and not first:
+                    outs.append(_regroup_segments(c, [x[1:] for x in o], nseg, s, dev))
+                else:
+                    outs.append(_merge_segments_64(c, o, nseg, mode, s, dev))
+            sources = [r for r, _ in outs]
+            seg_offs = [_seg_off_of(se) for _, se in outs]
+            first = False
     return sources[0], seg_offs[0][1:]
 
 
@@ -332,7 +341,12 @@ class MergedScanBatch:
     of it, count[q] counts the items of merge_all's answer, and records(q) / groups(q) /
     device_records(q) give every query's result, whichever path served it."""
 
-    def __init__(self, nq, merged, seg_end, limits, served, merge, sbs):
+    def __init__(self, nq, merged, seg_end, limits, served, merge, sbs, stream=None):
+        self._stream = stream      # the stream the batch was produced on: every host read goes through it
+        with torch.cuda.stream(stream):
+            self._init(nq, merged, seg_end, limits, served, merge, sbs)
+
+    def _init(self, nq, merged, seg_end, limits, served, merge, sbs):
         self.nq = nq
         self.grouped = isinstance(merged, Grouped)
         self.keys, self.key_end, self.vals, self.val_end = merged.keys, merged.key_end, merged.vals, merged.val_end
@@ -356,14 +370,19 @@ class MergedScanBatch:
 
     def _ends(self):
         if self._host is None:
-            self._host = (self.key_end.cpu().numpy(), self.val_end.cpu().numpy(),
-                          self.grp_end.cpu().numpy() if self.grouped else None)
+            with torch.cuda.stream(self._stream):
+                self._host = (self.key_end.cpu().numpy(), self.val_end.cpu().numpy(),
+                              self.grp_end.cpu().numpy() if self.grouped else None)
         return self._host
 
     def _view(self, q: int):
         """query q's reported items as a Grouped / DeviceRecords view of the batch's buffers"""
         if q in self._served:
             return self._served[q]
+        with torch.cuda.stream(self._stream):   # the offset shifts below are kernels: on the batch's stream
+            return self._view_on(q)
+
+    def _view_on(self, q: int):
         ke, ve, ge = self._ends()
         g0 = int(self._off[q])
         g1 = g0 + int(self._count[q])
@@ -375,14 +394,16 @@ class MergedScanBatch:
             b0 = int(ve[v0 - 1]) if v0 else 0
             b1 = int(ve[v1 - 1]) if v1 else 0
             return Grouped(self.keys[k0:k1], self.key_end[g0:g1] - k0, self.vals[b0:b1], self.val_end[v0:v1] - b0,
-                           self.grp_end[g0:g1] - v0)
+                           self.grp_end[g0:g1] - v0, self._stream)
         b0 = int(ve[g0 - 1]) if g0 else 0
         b1 = int(ve[g1 - 1]) if g1 else 0
-        return DeviceRecords(self.keys[k0:k1], self.key_end[g0:g1] - k0, self.vals[b0:b1], self.val_end[g0:g1] - b0)
+        return DeviceRecords(self.keys[k0:k1], self.key_end[g0:g1] - k0, self.vals[b0:b1], self.val_end[g0:g1] - b0,
+                             self._stream)
 
     def _bytes(self):
         if self._hostb is None:
-            self._hostb = (self.keys.cpu().numpy().tobytes(), self.vals.cpu().numpy().tobytes())
+            with torch.cuda.stream(self._stream):
+                self._hostb = (self.keys.cpu().numpy().tobytes(), self.vals.cpu().numpy().tobytes())
         return self._hostb
 
     def groups(self, q: int):
@@ -429,10 +450,11 @@ class MergedScanBatch:
 
     def device_records(self, q: int) -> DeviceRecords:
         """query q's merged records on the device (what encode.write_file takes)"""
-        if self.grouped:
-            return DeviceRecords.from_list(self.records(q), device=self.keys.device)
-        v = self._view(q)
-        return DeviceRecords(v.keys, v.key_end.contiguous(), v.vals, v.val_end.contiguous())
+        with torch.cuda.stream(self._stream):
+            if self.grouped:
+                return DeviceRecords.from_list(self.records(q), device=self.keys.device, stream=self._stream)
+            v = self._view(q)
+            return DeviceRecords(v.keys, v.key_end.contiguous(), v.vals, v.val_end.contiguous(), self._stream)
 
 
 def _cut_groups(r, m):
@@ -441,14 +463,15 @@ def _cut_groups(r, m):
         return r
     if m == 0:
         z = r.key_end[:0]
-        return Grouped(r.keys[:0], z, r.vals[:0], z, z) if isinstance(r, Grouped) else \
-            DeviceRecords(r.keys[:0], z, r.vals[:0], z)
-    kb = int(r.key_end[m - 1].item())
-    if isinstance(r, Grouped):
-        nv = int(r.grp_end[m - 1].item())
-        return Grouped(r.keys[:kb], r.key_end[:m], r.vals[: int(r.val_end[nv - 1].item())], r.val_end[:nv],
-                       r.grp_end[:m])
-    return DeviceRecords(r.keys[:kb], r.key_end[:m], r.vals[: int(r.val_end[m - 1].item())], r.val_end[:m])
+        return Grouped(r.keys[:0], z, r.vals[:0], z, z, r.stream) if isinstance(r, Grouped) else \
+            DeviceRecords(r.keys[:0], z, r.vals[:0], z, r.stream)
+    with torch.cuda.stream(r.stream):
+        kb = int(r.key_end[m - 1].item())
+        if isinstance(r, Grouped):
+            nv = int(r.grp_end[m - 1].item())
+            return Grouped(r.keys[:kb], r.key_end[:m], r.vals[: int(r.val_end[nv - 1].item())], r.val_end[:nv],
+                           r.grp_end[:m], r.stream)
+        return DeviceRecords(r.keys[:kb], r.key_end[:m], r.vals[: int(r.val_end[m - 1].item())], r.val_end[:m], r.stream)
 
 
 def _scan_records(reader) -> DeviceRecords:
@@ -505,8 +528,14 @@ class Merger:
     def _device(self):
         return self.sources[0].file.device if self.sources else None
 
+    def _s(self, stream=None):
+        """S of the stream contract for this Merger: `stream`, else Merger(stream=), else the current stream"""
+        return codec._stream_of(stream if stream is not None else self.stream, self._device())
+
     def _run(self, mode: str):
-        return merge_all([_scan_records(r) for r in self.sources], mode, self.stream, self._device())
+        s = self._s()
+        with torch.cuda.stream(s):   # the sources are scanned on the stream that merges them
+            return merge_all([_scan_records(r) for r in self.sources], mode, s, self._device())
 
     def groups(self) -> Grouped:
         """MultiIter's items, on the device"""
@@ -531,28 +560,35 @@ class Merger:
     def records(self) -> DeviceRecords:
         """the merged stream on the device (what encode.write_file takes)"""
         if callable(self.merge):
-            return DeviceRecords.from_list(self._merged_list(), device=self._device() or "cuda")
+            s = self._s()
+            return DeviceRecords.from_list(self._merged_list(), device=self._device() or "cuda", stream=s)
         return self._run(self.merge)
 
     def write_file(self, block_size: int = 8192, restart_interval: int = 16,
                    compression: int = CompressionType.None_) -> torch.Tensor:
         """the merged .mtbl file (device uint8), written by the device Writer"""
-        return encode.write_file(self.records(), block_size, restart_interval, stream=self.stream,
-                                 compression=compression)
+        s = self._s()
+        with torch.cuda.stream(s):   # records() and the Writer on one stream, also when self.stream is None
+            return encode.write_file(self.records(), block_size, restart_interval, stream=s, compression=compression)
 
     def write_into(self, writer) -> None:
         """Merger::write_into (src/merger.rs:149-156) for the host Writer"""
         r = self.records()
         if r.n == 0:
             return
-        writer.insert_batch(r.keys.cpu().numpy(), r.key_end.cpu().numpy().astype(np.uint64),
-                            r.vals.cpu().numpy(), r.val_end.cpu().numpy().astype(np.uint64))
+        with torch.cuda.stream(r.stream):
+            writer.insert_batch(r.keys.cpu().numpy(), r.key_end.cpu().numpy().astype(np.uint64),
+                                r.vals.cpu().numpy(), r.val_end.cpu().numpy().astype(np.uint64))
 
     # ---- batched reads of the merged view ----
     def _scan_merge(self, queries, max_blocks, max_records, stream, mode) -> MergedScanBatch:
         qs, limits = check_queries(queries, max_records)
+        s = self._s(stream)
+        with torch.cuda.stream(s):   # the sources' scans, the seek-path answers, the merges and the read-back: all on s
+            return self._scan_merge_on(qs, limits, max_blocks, s, mode)
+
+    def _scan_merge_on(self, qs, limits, max_blocks, s, mode) -> MergedScanBatch:
         nq = len(qs)
-        s = stream if stream is not None else self.stream
         # m + 1 records per source are enough for the first m items: a source's record at position
         # p >= m + 1 has at least p - 1 >= m distinct kept keys before it (the - 1: the empty key)
         per_src = None if all(m is None for m in limits) else [None if m is None else m + 1 for m in limits]
@@ -566,7 +602,7 @@ class Merger:
             recs, offs = [DeviceRecords.from_list([], device=dev)], [torch.zeros(nq + 1, dtype=torch.int64, device=dev)]
         merged, seg_end = merge_segments(recs, offs, mode, s, dev)
         served = {q: _cut_groups(merge_all(parts[q], mode, s, dev), limits[q]) for q in back}
-        return MergedScanBatch(nq, merged, seg_end, limits, served, self.merge, sbs)
+        return MergedScanBatch(nq, merged, seg_end, limits, served, self.merge, sbs, s)
 
     def scan_batch(self, queries, max_blocks: int = 64, max_records=None, stream=None) -> MergedScanBatch:
         """MergerIter over iter_from / get / iter_prefix / iter_range of every source, for a batch of

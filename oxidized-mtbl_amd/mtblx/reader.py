@@ -73,12 +73,14 @@ class Scan:
     vals: torch.Tensor
     key_end: torch.Tensor    # device int64 [nrec], global END offsets into keys
     val_end: torch.Tensor
+    stream: object = None    # the stream the tensors were produced on (None: whatever is current at the read)
 
     def records(self):
-        ke = self.key_end.cpu().numpy()
-        ve = self.val_end.cpu().numpy()
-        k = self.keys.cpu().numpy().tobytes()
-        v = self.vals.cpu().numpy().tobytes()
+        with torch.cuda.stream(self.stream):
+            ke = self.key_end.cpu().numpy()
+            ve = self.val_end.cpu().numpy()
+            k = self.keys.cpu().numpy().tobytes()
+            v = self.vals.cpu().numpy().tobytes()
         out, pk, pv = [], 0, 0
         for i in range(self.nrec):
             out.append((k[pk: ke[i]], v[pv: ve[i]]))
@@ -94,7 +96,8 @@ class ScanBatch:
     answered by iterator.bulk(); scan(q) / records(q) give every query's result, whichever path
     served it."""
 
-    def __init__(self, nq, keys, vals, key_end, val_end, rec_off, status, host, served):
+    def __init__(self, nq, keys, vals, key_end, val_end, rec_off, status, host, served, stream=None):
+        self._stream = stream      # the stream of the scan: scan(q) / records(q) work and read on it
         self.nq, self.keys, self.vals, self.key_end, self.val_end = nq, keys, vals, key_end, val_end
         self.rec_off, self.status = rec_off, status
         self._res = host           # mtblx_scan_result per query (host)
@@ -113,17 +116,19 @@ class ScanBatch:
         r = self._res[q]
         r0, n = int(r["rec_base"]), int(r["nrec"])
         k0, v0 = int(r["key_base"]), int(r["val_base"])
-        return Scan(END_NONE, "None", n, self.keys[k0: k0 + int(r["key_bytes"])],
-                    self.vals[v0: v0 + int(r["val_bytes"])], self.key_end[r0: r0 + n] - k0,
-                    self.val_end[r0: r0 + n] - v0)
+        with torch.cuda.stream(self._stream):   # the offset shifts are kernels
+            return Scan(END_NONE, "None", n, self.keys[k0: k0 + int(r["key_bytes"])],
+                        self.vals[v0: v0 + int(r["val_bytes"])], self.key_end[r0: r0 + n] - k0,
+                        self.val_end[r0: r0 + n] - v0, self._stream)
 
     def records(self, q: int):
         """query q's (key, value) pairs on the host (the batch is copied once)"""
         if q in self._served:
             return self._served[q].records()
         if self._host is None:
-            self._host = (self.keys.cpu().numpy().tobytes(), self.vals.cpu().numpy().tobytes(),
-                          self.key_end.cpu().numpy(), self.val_end.cpu().numpy())
+            with torch.cuda.stream(self._stream):
+                self._host = (self.keys.cpu().numpy().tobytes(), self.vals.cpu().numpy().tobytes(),
+                              self.key_end.cpu().numpy(), self.val_end.cpu().numpy())
         k, v, ke, ve = self._host
         r = self._res[q]
         r0, pk, pv = int(r["rec_base"]), int(r["key_base"]), int(r["val_base"])
@@ -242,8 +247,10 @@ class Reader:
                                          torch.tensor([clen.value], dtype=torch.int32, device=device),
                                          int(clen.value))
         self.index = codec.decode_blocks(self._ibatch)
-        torch.cuda.synchronize()
-        ist = int(self.index.status[0].item())
+        ist = int(self.index.status[0].item())   # synchronises the current stream, which ran the decode
+        # the decoded index is complete from here on and is read by calls on any stream: its host
+        # reads use the stream current at the read, not the constructor's (a call must not wait for that one)
+        self.index._stream = None
         if ist == _lib.ST_INVALID_BLOCK:
             raise MtblError(6)   # Block::init(index) -> InvalidBlock (src/reader.rs:76)
         self.index_status = ist
@@ -255,6 +262,21 @@ class Reader:
         self._regular = None
         self._ikeys = None
         self._irecs = None
+
+    # ------------------------------------------------------------------ streams ("Streams")
+    def _s(self, stream):
+        """S of the stream contract: `stream`, or the stream current on the file's device"""
+        return codec._stream_of(stream, self.file.device)
+
+    def _settle(self) -> None:
+        """Device state the Reader keeps across calls (the directory, the cached scan, the
+        decompressed-block tables and the on-demand arena) is built on the stream of the call that
+        first needs it and read by later calls on any stream: whoever builds or changes it drains
+        that stream once, so the state is complete before another stream can see it.  It drains
+        the CURRENT stream: correct only where the builder already runs under torch.cuda.stream(S),
+        as every public entry point arranges; a builder called outside that context would drain
+        the wrong stream."""
+        torch.cuda.current_stream(self.file.device).synchronize()
 
     # ------------------------------------------------------------------ directory
     def directory(self):
@@ -291,6 +313,7 @@ class Reader:
                 if rc != 0:
                     raise RuntimeError(f"mtblx_block_dir failed: {rc}")
             self._dir3 = (off[: self.nent], ln[: self.nent], st[: self.nent])
+            self._settle()
         return self._dir3
 
     # ------------------------------------------------------------------ iteration
@@ -334,6 +357,7 @@ class Reader:
         if n == 0:   # ReaderIntoIter::new with no index entry; a corrupt index panics at its first
             end = END_PANIC if self.index_status == _lib.ST_CORRUPT else END_NONE
             self._scan = iterator._assemble([], end, err, self.file.device)
+            self._settle()
             return self._scan
         parts, end, err, stopped = self._walk_blocks(0, n, first_exempt=True)
         if not stopped:
@@ -342,6 +366,7 @@ class Reader:
             elif self.index_status == _lib.ST_LOOP:
                 end = END_LOOP
         self._scan = iterator._assemble(parts, end, err, self.file.device)
+        self._settle()
         return self._scan
 
     def _walk_blocks(self, i0: int, i1: int, first_exempt: bool):
@@ -526,6 +551,7 @@ class Reader:
                 ts, tdo, tdl, tst = ts[ok], tdo[ok], tdl[ok], tst[ok]
                 order = torch.argsort(ts, stable=True)
                 self._dtab = (ts[order], tdo[order], tdl[order], tst[order], int(order.numel()), buf)
+                self._settle()
             return self._dtab
         if self._dtab is None:
             off, ln, st = self._framing()
@@ -539,6 +565,7 @@ class Reader:
             t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)
             self._dtab = (t(start[order], np.int64), t(doff[order], np.int64), t(dlen[order], np.int64),
                           t(zst[order], np.int32), int(order.size), torch.from_numpy(buf).to(dev))
+            self._settle()
         return self._dtab
 
     def _dtab_add(self, starts, sizes):
@@ -572,6 +599,7 @@ class Reader:
         extra = torch.from_numpy(np.concatenate(parts) if parts else np.zeros(0, np.uint8)).to(dev)
         self._dtab = (t(start[order]), t(doff[order]), t(dlen[order]), t(zst[order]), int(order.size),
                       torch.cat([dec, extra]))
+        self._settle()
 
     # ------------------------------------------------------------------ device staging (Snappy)
     def _stage_plan(self, off, ln, st, bad, sel, stream=None):
@@ -638,6 +666,7 @@ class Reader:
                     raise RuntimeError(f"mtblx_dir_ascends failed: {rc}")
                 if int(viol.item()) == 0:
                     self._od = _OnDemand(self.nent, torch.from_numpy(np.ascontiguousarray(eoffs, np.int64)).to(dev), dev)
+                    self._settle()
         return self._od
 
     @property
@@ -722,6 +751,7 @@ class Reader:
         if rc != 0:
             raise RuntimeError(f"mtblx_table_gather failed: {rc}")
         od.table = (ts, tdo, tdl, tst, m, od.arena)
+        self._settle()   # the arena and the table changed: complete before a call on another stream reads them
 
     def _od_missing(self, starts, stream=None) -> bool:
         """a lookup reached stored blocks the on-demand table lacks (the touch is a hint): stage
@@ -749,14 +779,22 @@ class Reader:
         """Reader::get for every key at once on the device (mtblx_get / mtblx_get_decompressed,
         f2).  -> (status int32 [nq] (GET_*), val_off int64 [nq], val_len int64 [nq]) device
         tensors; the value of a FOUND query q is value_source[val_off[q] : val_off[q] +
-        val_len[q]] (the file itself unless it is compressed)."""
+        val_len[q]] (the file itself unless it is compressed).  Asynchronous on `stream` for an
+        uncompressed file; a compressed one synchronises `stream` for the on-demand table."""
+        stream = self._s(stream)
+        with torch.cuda.stream(stream):   # queries, outputs, table work and the MISSING read-backs: all on `stream`
+            return self._get_batch(keys, stream)
+
+    def _get_batch(self, keys, stream):
         dev = self.file.device
         ks = [bytes(k) for k in keys]
         nq = len(ks)
         blob = b"".join(ks) or b"\0"
-        kb = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
-        ke = torch.tensor(np.cumsum([len(k) for k in ks], dtype=np.int64) if nq else [0], dtype=torch.int64,
-                          device=dev)
+        # through pinned memory, without blocking: a copy from pageable memory would make the host wait
+        # for everything queued on `stream` before it, and the uncompressed lookup only enqueues
+        up = lambda a: torch.from_numpy(a).pin_memory().to(dev, non_blocking=True)   # noqa: E731
+        kb = up(np.frombuffer(blob, np.uint8).copy())
+        ke = up(np.cumsum([len(k) for k in ks], dtype=np.int64) if nq else np.zeros(1, np.int64))
         n = max(nq, 1)
         st = torch.zeros(n, dtype=torch.int32, device=dev)
         vo = torch.zeros(n, dtype=torch.int64, device=dev)
@@ -925,7 +963,9 @@ class Reader:
         """The plan of scan_batch alone: (status int32, nrec, key_bytes, val_bytes int64) [nq] on the
         device.  Queries that are not SCAN_OK count 0: scan_batch answers them through bulk()."""
         nq = len(queries)
-        res = self._scan_plan(queries, max_blocks, None, stream)[0]
+        stream = self._s(stream)
+        with torch.cuda.stream(stream):   # mtblx_scan_plan returns its totals: it synchronises `stream`, so the
+            res = self._scan_plan(queries, max_blocks, None, stream)[0]   # workspace may go back to the allocator
         w = res.view(torch.int64).view(-1, 8)[:nq]
         return res.view(torch.int32).view(-1, 16)[:nq, 0], w[:, 1], w[:, 2], w[:, 3]
 
@@ -936,7 +976,14 @@ class Reader:
         (None = no limit).  A query the kernels hand back -- SCAN_LARGE: more than `max_blocks` data
         blocks; SCAN_FALLBACK: somewhere the reference panics, errs or loops -- is answered by
         iterator.bulk() with the limit applied; so is every query when the index block is not
-        regular.  ("get", k) is Reader::get: at most one record."""
+        regular.  ("get", k) is Reader::get: at most one record.  Everything -- the uploads, the
+        on-demand staging, plan and emit, the read-backs and the seek-path answers -- runs on
+        `stream` (default: the current stream), which the call synchronises."""
+        stream = self._s(stream)
+        with torch.cuda.stream(stream):
+            return self._scan_batch(list(queries), max_blocks, max_records, stream)
+
+    def _scan_batch(self, queries, max_blocks, max_records, stream) -> "ScanBatch":
         from . import iterator
         dev = self.file.device
         queries = list(queries)
@@ -948,9 +995,10 @@ class Reader:
             if kind == "get":
                 m = 1 if m is None else min(m, 1)
             if m is None or s.nrec < m or (m == 0 and s.end != END_NONE):
+                s.stream = stream
                 return s
             p = iterator._cut_part((s.keys, s.vals, s.key_end, s.val_end, s.nrec), m)
-            return Scan(END_NONE, "None", m, p[0], p[1], p[2], p[3])
+            return Scan(END_NONE, "None", m, p[0], p[1], p[2], p[3], stream)
 
         z8 = torch.zeros(0, dtype=torch.uint8, device=dev)
         z64 = torch.zeros(0, dtype=torch.int64, device=dev)
@@ -960,7 +1008,8 @@ class Reader:
             host = np.zeros(nq, np.dtype(_lib.ScanResult))
             host["status"] = _lib.SCAN_FALLBACK
             return ScanBatch(nq, z8, z8, z64, z64, torch.zeros(nq + 1, dtype=torch.int64, device=dev),
-                             torch.full((nq,), _lib.SCAN_FALLBACK, dtype=torch.int32, device=dev), host, served)
+                             torch.full((nq,), _lib.SCAN_FALLBACK, dtype=torch.int32, device=dev), host, served,
+                             stream)
         res, totals, ws, wsb, limits, tab, keep = self._scan_plan(queries, max_blocks, max_records, stream)
         nrec, kbytes, vbytes = totals[0], totals[1], totals[2]
         buf = torch.empty(kbytes + vbytes + 16 * nrec + 8, dtype=torch.uint8, device=dev)   # ends first: aligned
@@ -978,7 +1027,9 @@ class Reader:
                                         C.c_void_p(codec._stream_handle(stream)))
         if rc != 0:
             raise RuntimeError(f"mtblx_scan_emit failed: {rc}")
-        host = np.frombuffer(res.cpu().numpy().tobytes(), np.dtype(_lib.ScanResult))[:nq]   # the one read-back
+        # the one read-back: on `stream`, behind the emit, so it synchronises the emit too -- the flags
+        # word is complete, and the workspace may go back to the allocator when this call returns
+        host = np.frombuffer(res.cpu().numpy().tobytes(), np.dtype(_lib.ScanResult))[:nq]
         fl = int(flags[0].item())
         if fl:
             raise RuntimeError(f"mtblx_scan_emit: flags {fl}")
@@ -986,7 +1037,7 @@ class Reader:
         rec_off = torch.cat([w[:, 4], torch.tensor([nrec], dtype=torch.int64, device=dev)])
         status = res.view(torch.int32).view(-1, 16)[:nq, 0]
         served = {int(q): limited(int(q), limits[int(q)]) for q in np.nonzero(host["status"] != _lib.SCAN_OK)[0]}
-        return ScanBatch(nq, keys, vals, key_end, val_end, rec_off, status, host, served)
+        return ScanBatch(nq, keys, vals, key_end, val_end, rec_off, status, host, served, stream)
 
     def into_iter(self, kind: str = "iter", key: bytes = b"", key2: bytes = b""):
         """the stateful ReaderIntoIter (next() / seek()), see iterator.ReaderIntoIter"""

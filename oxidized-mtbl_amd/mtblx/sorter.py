@@ -96,14 +96,15 @@ def sort_records(recs: DeviceRecords, mode, stream=None):
         if m in (_lib.MERGE_FIRST, _lib.MERGE_LAST) and groups:   # vals was sized by its upper bound
             vals = vals[: int(val_end[-1].item())]
     if grouped:
-        return Grouped(keys, key_end, vals, val_end, grp_end)
-    return DeviceRecords(keys, key_end, vals, val_end)
+        return Grouped(keys, key_end, vals, val_end, grp_end, s)
+    return DeviceRecords(keys, key_end, vals, val_end, s)
 
 
 def _apply(merge, grouped: Grouped, device) -> DeviceRecords:
-    """a callable merge function over MultiIter-shaped groups: groups of one pass through (:166-170)"""
+    """a callable merge function over MultiIter-shaped groups: groups of one pass through (:166-170);
+    read back and uploaded again on the stream the groups were produced on"""
     return DeviceRecords.from_list([(k, vs[0] if len(vs) == 1 else bytes(merge(k, vs))) for k, vs in grouped.to_list()],
-                                   device=device)
+                                   device=device, stream=grouped.stream)
 
 
 class SorterBuilder:
@@ -163,6 +164,11 @@ class Sorter:
         self.chunk_sizes, self.merges = [], 0
         self._done = False
 
+    def _s(self):
+        """S of the stream contract: Sorter(stream=), else the stream current at the call.  Device
+        batches handed to insert_batch must be ready on it; staging, sorts and merges all run on it."""
+        return codec._stream_of(self.stream, self.device)
+
     @staticmethod
     def builder(merge, device="cuda", stream=None) -> SorterBuilder:   # :108-110
         return SorterBuilder(merge, device, stream)
@@ -188,6 +194,10 @@ class Sorter:
         them, or device tensors (uint8 / int64).  Same effect as insert() record by record; the
         cut positions come from the cumulative lengths, one step per cut or capacity doubling."""
         dev = isinstance(key_end, torch.Tensor)
+        with torch.cuda.stream(self._s() if dev else None):   # the offset sums, searches and reads of a device batch
+            self._insert_batch(keys, key_end, vals, val_end, dev)
+
+    def _insert_batch(self, keys, key_end, vals, val_end, dev) -> None:
         if dev:
             ke, ve = key_end.to(torch.int64), val_end.to(torch.int64)
             cs = ke + ve
@@ -264,21 +274,26 @@ class Sorter:
 
     # ---- write_chunk (:142-197)
     def write_chunk(self) -> None:
+        with torch.cuda.stream(self._s()):   # the pieces are joined on the stream that sorts them
+            self._write_chunk(self._s())
+
+    def _write_chunk(self, s) -> None:
         recs = self._pending()
         self.chunk_sizes.append(recs.n)
         if callable(self.merge):
-            chunk = _apply(self.merge, sort_records(recs, "groups", self.stream), self.device)   # :152-188
+            chunk = _apply(self.merge, sort_records(recs, "groups", s), self.device)   # :152-188
         else:
-            chunk = sort_records(recs, self.merge, self.stream)
+            chunk = sort_records(recs, self.merge, s)
         self.chunks.append(chunk)                           # :191
         self.entry_bytes = 0                                # :192
         self._len = 0                                       # :155 drain(..): the capacity stays
 
     def _merge_all(self) -> DeviceRecords:
         """a Merger over the chunks, oldest first (MergerIter with its empty-key quirk)"""
+        s = self._s()
         if callable(self.merge):
-            return _apply(self.merge, merge_all(self.chunks, "groups", self.stream, self.device), self.device)
-        return merge_all(self.chunks, self.merge, self.stream, self.device)
+            return _apply(self.merge, merge_all(self.chunks, "groups", s, self.device), self.device)
+        return merge_all(self.chunks, self.merge, s, self.device)
 
     # ---- merge_chunks (:199-233)
     def merge_chunks(self) -> None:
@@ -301,13 +316,15 @@ class Sorter:
     def write_file(self, block_size: int = 8192, restart_interval: int = 16,
                    compression: int = CompressionType.None_) -> torch.Tensor:
         """the .mtbl file (device uint8), written by the device Writer"""
-        return encode.write_file(self.records(), block_size, restart_interval, stream=self.stream,
-                                 compression=compression)
+        s = self._s()
+        with torch.cuda.stream(s):   # the last chunk, the merge and the Writer on one stream
+            return encode.write_file(self.records(), block_size, restart_interval, stream=s, compression=compression)
 
     def write_into(self, writer) -> None:
         """Sorter::write_into (:235-242) for the host Writer"""
         r = self.records()
         if r.n == 0:
             return
-        writer.insert_batch(r.keys.cpu().numpy(), r.key_end.cpu().numpy().astype(np.uint64),
-                            r.vals.cpu().numpy(), r.val_end.cpu().numpy().astype(np.uint64))
+        with torch.cuda.stream(r.stream):
+            writer.insert_batch(r.keys.cpu().numpy(), r.key_end.cpu().numpy().astype(np.uint64),
+                                r.vals.cpu().numpy(), r.val_end.cpu().numpy().astype(np.uint64))

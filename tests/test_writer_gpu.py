@@ -123,3 +123,47 @@ def test_cfg3_scheme_file_roundtrip(oracle):
     torch.cuda.synchronize()
     assert s.end == reader.END_NONE and s.nrec == len(recs)
     assert s.records() == recs
+
+
+def test_encode_index_refuses_a_cut_whose_ends_leave_the_records(oracle):
+    """mtblx_encode_index checks blk_rec[0] <= blk_rec[nblk] <= rec->n before it launches anything
+    (include/mtblx.h): a cut that ends one record past the records, or whose first entry lies past
+    its last, returns MTBLX_E_INVAL and leaves `file` and *file_len untouched; the plan's own cut
+    gives the Writer's file."""
+    import ctypes as C
+    import torch
+    encode = _dev()
+    from mtblx import _lib, codec
+    L = _lib.lib()
+    records = corpus.random_records(np.random.default_rng(3), 500, 1, 20, 0, 40)
+    recs = encode.DeviceRecords.from_list(records)
+    blk = encode.plan(recs, 1024, 16)
+    nblk = int(blk.numel()) - 1
+    assert nblk >= 3
+    e = encode.encode_blocks(recs, blk, 16).check()
+    data_bytes = int(e.totals[0].item())
+    cap = data_bytes + int(recs.keys.numel()) + 36 * nblk + 1024
+    rc_ = recs.cstruct()
+    u = codec._u
+
+    def index(cut):
+        file = torch.full((cap,), 0xA5, dtype=torch.uint8, device="cuda")
+        n = C.c_uint64(77)
+        torch.cuda.synchronize()
+        rc = L.mtblx_encode_index(C.byref(rc_), C.c_void_p(u(cut)), nblk, 1024, 16, C.c_void_p(u(e.out)), 0, data_bytes,
+                                  C.c_void_p(u(e.blk_off)), C.c_void_p(u(e.blk_len)), C.c_void_p(file.data_ptr()), cap,
+                                  C.byref(n), C.c_void_p(codec._stream_handle(None)))
+        torch.cuda.synchronize()
+        return rc, int(n.value), file
+
+    past = blk.clone()
+    past[-1] = recs.n + 1                       # the last block would end one record past the records
+    inverted = blk.clone()
+    inverted[0] = recs.n + 5                    # first entry past the last
+    for cut in (past, inverted):
+        rc, n, file = index(cut)
+        assert rc == _lib.MTBLX_E_INVAL and n == 77
+        assert bool((file == 0xA5).all())       # refused before the data region was copied or a kernel ran
+    rc, n, file = index(blk)
+    assert rc == _lib.MTBLX_OK
+    assert file[:n].cpu().numpy().tobytes() == oracle.write_file(records, 1024, 16)
