@@ -307,6 +307,15 @@ struct Record {   // a (key, value) pair served by the iterators (views into the
 };
 
 class Reader;
+struct MergeReduce;
+
+// one query's answer of Reader::reduce_batch (mtblx.h "Aggregating scans"): nrec records yielded, nbad of
+// them with a value of another length than 8 * nfields (left out and counted), fields[f] = op[f] over
+// field f of the others (the op's identity over nothing); fields past nfields are 0
+struct Reduced {
+  uint64_t fields[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t nrec = 0, nbad = 0;
+};
 
 // one query of Reader::scan_batch
 struct ScanQuery {
@@ -445,6 +454,12 @@ class Reader {
   using Records = std::vector<std::pair<Bytes, Bytes>>;
   std::vector<Records> scan_batch(const std::vector<ScanQuery>& queries, uint32_t max_blocks = 64,
                                   std::vector<uint8_t>* served = nullptr) const;
+  // scan_batch that aggregates (mtblx_scan_reduce): per query, `reduce` folded over the values of the
+  // records scan_batch would return, in one walk that materialises no record.  The queries the kernel
+  // hands back, and every query of a compressed file or an irregular index, go the way scan_batch
+  // sends them and their records are folded on the host.  served as in scan_batch.
+  std::vector<Reduced> reduce_batch(const std::vector<ScanQuery>& queries, const MergeReduce& reduce,
+                                    uint32_t max_blocks = 64, std::vector<uint8_t>* served = nullptr) const;
   // blocks this Reader has decompressed on the host so far (Zlib / Zstd; a Snappy file's blocks are
   // decompressed on the device when the iterator loads them, and on the host only by a seek's own
   // block and by blocks >= 4 GiB)
@@ -1228,6 +1243,25 @@ inline Reader::Records Reader::scan_one(const ScanQuery& q) const {
   return out;
 }
 
+namespace detail {
+// the queries as mtblx_scan_plan / mtblx_scan_reduce take them
+struct ScanPack {
+  Bytes kb, k2b;
+  std::vector<uint64_t> ke, k2e, mr;
+  std::vector<int32_t> type;
+  explicit ScanPack(const std::vector<ScanQuery>& qs) : ke(qs.size()), k2e(qs.size()), mr(qs.size()), type(qs.size()) {
+    for (size_t q = 0; q < qs.size(); ++q) {
+      type[q] = (int32_t)qs[q].kind;
+      kb.insert(kb.end(), qs[q].key.begin(), qs[q].key.end());
+      if (qs[q].kind == ScanQuery::Range) k2b.insert(k2b.end(), qs[q].key2.begin(), qs[q].key2.end());
+      ke[q] = kb.size();
+      k2e[q] = k2b.size();
+      mr[q] = qs[q].max_records ? *qs[q].max_records : ~0ull;
+    }
+  }
+};
+}  // namespace detail
+
 inline std::vector<Reader::Records> Reader::scan_batch(const std::vector<ScanQuery>& qs, uint32_t max_blocks,
                                                        std::vector<uint8_t>* served) const {
   using namespace detail;
@@ -1239,19 +1273,10 @@ inline std::vector<Reader::Records> Reader::scan_batch(const std::vector<ScanQue
     for (uint32_t q = 0; q < nq; ++q) out[q] = scan_one(qs[q]);
     return out;
   }
-  Bytes kb, k2b;
-  std::vector<uint64_t> ke(nq), k2e(nq), mr(nq);
-  std::vector<int32_t> type(nq);
-  for (uint32_t q = 0; q < nq; ++q) {
-    type[q] = (int32_t)qs[q].kind;
-    kb.insert(kb.end(), qs[q].key.begin(), qs[q].key.end());
-    if (qs[q].kind == ScanQuery::Range) k2b.insert(k2b.end(), qs[q].key2.begin(), qs[q].key2.end());
-    ke[q] = kb.size();
-    k2e[q] = k2b.size();
-    mr[q] = qs[q].max_records ? *qs[q].max_records : ~0ull;
-  }
-  const DevBuf d_k = upload_key(kb), d_ke = upload(ke.data(), nq), d_k2 = upload_key(k2b), d_k2e = upload(k2e.data(), nq),
-               d_mr = upload(mr.data(), nq);
+  const ScanPack pack(qs);
+  const std::vector<int32_t>& type = pack.type;
+  const DevBuf d_k = upload_key(pack.kb), d_ke = upload(pack.ke.data(), nq), d_k2 = upload_key(pack.k2b),
+               d_k2e = upload(pack.k2e.data(), nq), d_mr = upload(pack.mr.data(), nq);
   const size_t wsb = mtblx_scan_workspace_bytes(nq);
   const DevBuf ws(wsb), d_res(sizeof(mtblx_scan_result) * (size_t)nq);   // hipMalloc aligns to 256 bytes
   uint64_t totals[4];
@@ -1335,6 +1360,25 @@ inline mtblx_reduce reduce_spec(const MergeReduce& r) {
     spec.op[f] = static_cast<uint8_t>(r.ops[f]);
   }
   return spec;
+}
+// Reduce.fold of the Python surface: the aggregating scans' semantics on the host
+inline Reduced fold_host(const mtblx_reduce& spec, const Reader::Records& recs) {
+  Reduced r;
+  for (uint32_t f = 0; f < spec.nfields; ++f) r.fields[f] = spec.op[f] == MTBLX_REDUCE_MIN ? ~0ull : 0ull;
+  for (const auto& kv : recs) {
+    ++r.nrec;
+    if (kv.second.size() != 8u * spec.nfields) {
+      ++r.nbad;
+      continue;
+    }
+    for (uint32_t f = 0; f < spec.nfields; ++f) {
+      uint64_t x = 0;
+      for (int b = 7; b >= 0; --b) x = (x << 8) | kv.second[8 * f + b];
+      uint64_t& a = r.fields[f];
+      a = spec.op[f] == MTBLX_REDUCE_SUM ? a + x : spec.op[f] == MTBLX_REDUCE_MIN ? (x < a ? x : a) : (x > a ? x : a);
+    }
+  }
+  return r;
 }
 // one plan + emit over sources [i0, i1) (at most MTBLX_MERGE_MAX_SOURCES); with a reduce spec the
 // emit is mtblx_merge_emit_reduce and `mode` is MTBLX_MERGE_FIRST, whose layout it has
@@ -1539,6 +1583,45 @@ inline SegGroups merge_seg_all(std::vector<HostGroups> src, SegOffsets off, uint
   return r;
 }
 }  // namespace detail
+
+inline std::vector<Reduced> Reader::reduce_batch(const std::vector<ScanQuery>& qs, const MergeReduce& reduce,
+                                                 uint32_t max_blocks, std::vector<uint8_t>* served) const {
+  using namespace detail;
+  const mtblx_reduce spec = reduce_spec(reduce);   // refused before any device work
+  const uint32_t nq = (uint32_t)qs.size(), nf = spec.nfields;
+  std::vector<Reduced> out(nq);
+  if (served) served->assign(nq, 0);
+  if (nq == 0) return out;
+  if (meta_.compression_algorithm != 0 || !regular()) {
+    for (uint32_t q = 0; q < nq; ++q) out[q] = fold_host(spec, scan_one(qs[q]));
+    return out;
+  }
+  const ScanPack pk(qs);
+  const DevBuf d_k = upload_key(pk.kb), d_ke = upload(pk.ke.data(), nq), d_k2 = upload_key(pk.k2b),
+               d_k2e = upload(pk.k2e.data(), nq), d_mr = upload(pk.mr.data(), nq);
+  const size_t wsb = mtblx_scan_workspace_bytes(nq);
+  const DevBuf ws(wsb), d_res(sizeof(mtblx_scan_result) * (size_t)nq), d_f(8 * (size_t)nq * nf), d_nb(8 * (size_t)nq);
+  uint64_t totals[4];
+  abi_check(mtblx_scan_reduce(dfile_.as<uint8_t>(), file_.size(), version_, verify_ ? 1 : 0, index_off_, index_len_,
+                              nullptr, nullptr, nullptr, nullptr, 0, nullptr, pk.type.data(), d_k.as<uint8_t>(),
+                              d_ke.as<uint64_t>(), d_k2.as<uint8_t>(), d_k2e.as<uint64_t>(), d_mr.as<uint64_t>(),
+                              max_blocks, nq, d_res.as<mtblx_scan_result>(), totals, ws.p, wsb, &spec,
+                              d_f.as<uint64_t>(), d_nb.as<uint64_t>(), nullptr),
+            "mtblx_scan_reduce");
+  const auto res = download<mtblx_scan_result>(d_res.p, nq);   // the call has synchronised
+  const auto hf = download<uint64_t>(d_f.p, (size_t)nq * nf), hb = download<uint64_t>(d_nb.p, nq);
+  for (uint32_t q = 0; q < nq; ++q) {
+    if (res[q].status != MTBLX_SCAN_OK) {
+      out[q] = fold_host(spec, scan_one(qs[q]));
+      continue;
+    }
+    if (served) (*served)[q] = 1;
+    for (uint32_t f = 0; f < nf; ++f) out[q].fields[f] = hf[(size_t)q * nf + f];
+    out[q].nrec = res[q].nrec;
+    out[q].nbad = hb[q];
+  }
+  return out;
+}
 
 class Merger;
 class MergerBuilder {   // src/merger.rs:66-94

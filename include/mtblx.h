@@ -44,7 +44,8 @@ extern "C" {
 #define MTBLX_ABI_VERSION 3   /* 3: the block cut takes a caller-owned workspace (round 6).  Still 3 with
                                  mtblx_decode_blocks_valpos / mtblx_pipe_decode_valpos and with the
                                  mtblx_merge_*, mtblx_sort_*, mtblx_scan_* and mtblx_stage_* calls (the two
-                                 mtblx_*_emit_reduce among them): added symbols, no existing one changed */
+                                 mtblx_*_emit_reduce, mtblx_scan_reduce and mtblx_reduce_segments among
+                                 them): added symbols, no existing one changed */
 
 /* ---- API return codes ---- */
 #define MTBLX_OK 0
@@ -804,6 +805,54 @@ int mtblx_merge_seg_emit_reduce(const mtblx_records* src, const uint64_t* const*
 int mtblx_merge_seg_plan_timed(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
                                uint32_t nseg, uint64_t* totals, uint64_t* seg_end, void* workspace, size_t ws_bytes,
                                void* stream, float* phase_ms, uint32_t phase_cap);
+
+/* ---- Aggregating scans: a reduce spec folded over all the records a query matches ----
+ * (csrc/scan.hip, csrc/reduce_seg.hip, DESIGN.md §4 "Aggregating scans").  The spec is the
+ * mtblx_reduce of the device merge functions: F = nfields little-endian u64 fields, W = 8 * F.  For
+ * one query (or one segment), over the records it yields:
+ *    nrec       the records yielded (mtblx_scan_result.nrec; the segment's length);
+ *    nbad       those among them whose value is not exactly W bytes long: left out of the reduction
+ *               and counted.  "A group of one passes through" does not apply: nothing passes through;
+ *    fields[f]  op[f] over field f of the nrec - nbad other values; over nothing, the op's identity
+ *               (0 for SUM and MAX, 2^64 - 1 for MIN).
+ * The results are exact and the ops associative and commutative: no result depends on evaluation
+ * order, tile size or which of the two calls served the query.
+ *
+ * mtblx_scan_reduce is mtblx_scan_plan (same arguments, same res[], same totals, synchronous) whose
+ * walk also reduces: where it counts a record it folds the record's value, read where it lies in the
+ * block, into fields[q * F + f] and nbad[q] (device, [nq * F] and [nq]).  No key is materialised and
+ * there is no second walk and no output buffer.  A query that ends LARGE or FALLBACK has zero fields
+ * and zero nbad, as it has zero counts.  The workspace is left planned exactly as mtblx_scan_plan
+ * leaves it: a caller who also wants the records follows with mtblx_scan_emit over it.
+ * MTBLX_E_INVAL before any device call: everything mtblx_scan_plan refuses, nfields 0 or above
+ * MTBLX_REDUCE_MAX_FIELDS, an op above MTBLX_REDUCE_MAX, NULL spec / fields / nbad, fields or nbad not
+ * 8-byte aligned.
+ *
+ * mtblx_reduce_segments (asynchronous, no workspace) reduces segments of any mtblx_records on the
+ * device: segment s = records [seg_lo[s], seg_hi[s]) (device u64 [nseg]), with seg_lo[s] <= seg_hi[s]
+ * <= seg_lo[s + 1] and seg_hi[nseg - 1] <= n; records in no segment bring nothing.  fields (device
+ * [nseg * F]) and nbad (device [nseg]) are 8-byte aligned arrays the call initialises itself.  A
+ * segment array that breaks the rule sets MTBLX_REDUCE_BADSEG in *flags (device u32, zeroed by the
+ * call) and fields / nbad are left as they were.  A workgroup owns MTBLX_REDUCE_SEG_TILE consecutive
+ * records, so one segment of a million records costs what a million segments cost.
+ * n < MTBLX_MERGE_MAX_RECORDS.  nseg == 0: MTBLX_OK, nothing written; n == 0: the identities.
+ * MTBLX_E_INVAL before any device call: a bad spec, NULL recs / fields / nbad / flags, NULL seg_lo or
+ * seg_hi with nseg != 0, n too large, nseg above MTBLX_REDUCE_MAX_SEGMENTS, n != 0 with a NULL val_end
+ * (vals may be NULL where every value is empty; keys and key_end are not read), and fields, nbad,
+ * seg_lo, seg_hi or val_end not 8-byte aligned (flags: 4-byte). */
+#define MTBLX_REDUCE_BADSEG 8u           /* *flags of mtblx_reduce_segments: a bad segment array     */
+#define MTBLX_REDUCE_SEG_TILE 1024       /* records per workgroup of mtblx_reduce_segments           */
+#define MTBLX_REDUCE_MAX_SEGMENTS 0xFFFFFF00u   /* nseg of mtblx_reduce_segments: 2^32 - 256 at most   */
+int mtblx_scan_reduce(const uint8_t* file, uint64_t file_len, uint32_t version, int verify, uint64_t index_off,
+                      uint64_t index_len, const uint64_t* tab_start, const uint64_t* tab_doff, const uint64_t* tab_dlen,
+                      const int32_t* tab_st, uint32_t ntab, const uint8_t* dec, const int32_t* type,
+                      const uint8_t* keys, const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
+                      const uint64_t* max_records, uint32_t max_blocks, uint32_t nq, mtblx_scan_result* res,
+                      uint64_t* totals, void* workspace, size_t ws_bytes, const mtblx_reduce* spec, uint64_t* fields,
+                      uint64_t* nbad, void* stream);
+int mtblx_reduce_segments(const mtblx_records* recs, const uint64_t* seg_lo, const uint64_t* seg_hi, uint32_t nseg,
+                          const mtblx_reduce* spec, uint64_t* fields, uint64_t* nbad, uint32_t* flags, void* stream);
+uint32_t mtblx_reduce_seg_tile(void);    /* MTBLX_REDUCE_SEG_TILE of the library that is loaded      */
 
 /* ---- snappy raw decompression on the device (f4) ----
  * Reader::block's decompression step for CompressionType::Snappy (src/reader.rs:166-170 ->

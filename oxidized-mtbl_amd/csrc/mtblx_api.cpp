@@ -335,12 +335,12 @@ static int scan_check(const uint8_t* file, uint32_t version, const uint64_t* tab
   return MTBLX_OK;
 }
 
-extern "C" int mtblx_scan_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify, uint64_t index_off,
-                               uint64_t index_len, const uint64_t* tab_start, const uint64_t* tab_doff,
-                               const uint64_t* tab_dlen, const int32_t* tab_st, uint32_t ntab, const uint8_t* dec,
-                               const int32_t* type, const uint8_t* keys, const uint64_t* key_end, const uint8_t* keys2,
-                               const uint64_t* key2_end, const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
-                               mtblx_scan_result* res, uint64_t* totals, void* ws, size_t wsb, void* stream) {
+// what mtblx_scan_plan and mtblx_scan_reduce check alike; MTBLX_OK: the totals are zeroed
+static int scan_plan_check(const uint8_t* file, uint32_t version, const uint64_t* tab_start, const uint64_t* tab_doff,
+                           const uint64_t* tab_dlen, const int32_t* tab_st, uint32_t ntab, const uint8_t* dec,
+                           const int32_t* type, const uint8_t* keys, const uint64_t* key_end, const uint8_t* keys2,
+                           const uint64_t* key2_end, uint32_t nq, const mtblx_scan_result* res, uint64_t* totals,
+                           const void* ws, size_t wsb) {
   if (!totals) return MTBLX_E_INVAL;
   const int c = scan_check(file, version, tab_start, tab_doff, tab_dlen, tab_st, ntab, dec, nq, ws, wsb);
   if (c != MTBLX_OK) return c;
@@ -350,6 +350,18 @@ extern "C" int mtblx_scan_plan(const uint8_t* file, uint64_t file_len, uint32_t 
     if (type[q] == 3 && (!keys2 || !key2_end)) return MTBLX_E_INVAL;
   }
   memset(totals, 0, 4 * sizeof(uint64_t));
+  return MTBLX_OK;
+}
+
+extern "C" int mtblx_scan_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify, uint64_t index_off,
+                               uint64_t index_len, const uint64_t* tab_start, const uint64_t* tab_doff,
+                               const uint64_t* tab_dlen, const int32_t* tab_st, uint32_t ntab, const uint8_t* dec,
+                               const int32_t* type, const uint8_t* keys, const uint64_t* key_end, const uint8_t* keys2,
+                               const uint64_t* key2_end, const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
+                               mtblx_scan_result* res, uint64_t* totals, void* ws, size_t wsb, void* stream) {
+  const int c = scan_plan_check(file, version, tab_start, tab_doff, tab_dlen, tab_st, ntab, dec, type, keys, key_end,
+                                keys2, key2_end, nq, res, totals, ws, wsb);
+  if (c != MTBLX_OK) return c;
   if (nq == 0) return MTBLX_OK;
   return mtblx_scan_impl_plan(file, file_len, version, verify, index_off, index_len, tab_start, tab_doff, tab_dlen,
                               tab_st, ntab, dec, type, keys, key_end, keys2, key2_end, max_records, max_blocks, nq, res,
@@ -369,6 +381,68 @@ extern "C" int mtblx_scan_emit(const uint8_t* file, uint64_t file_len, uint32_t 
   if (nq == 0) return MTBLX_OK;
   return mtblx_scan_impl_emit(file, file_len, version, index_off, index_len, tab_start, tab_doff, tab_dlen, tab_st,
                               ntab, dec, nq, out, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- aggregating scans (csrc/scan.hip, csrc/reduce_seg.hip): the spec and the outputs are checked
+// before any HIP call ----
+extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
+                                      uint64_t index_off, uint64_t index_len, const uint64_t* tab_start,
+                                      const uint64_t* tab_doff, const uint64_t* tab_dlen, const int32_t* tab_st,
+                                      uint32_t ntab, const uint8_t* dec, const int32_t* type, const uint8_t* keys,
+                                      const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
+                                      const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
+                                      mtblx_scan_result* res, uint64_t* totals, void* ws, const mtblx_reduce* spec,
+                                      uint64_t* fields, uint64_t* nbad, hipStream_t s);
+extern "C" int mtblx_reduce_seg_impl(const mtblx_records* recs, const uint64_t* seg_lo, const uint64_t* seg_hi,
+                                     uint32_t nseg, const mtblx_reduce* spec, uint64_t* fields, uint64_t* nbad,
+                                     uint32_t* flags, hipStream_t s);
+
+static int spec_check(const mtblx_reduce* spec) {
+  if (!spec || spec->nfields < 1 || spec->nfields > MTBLX_REDUCE_MAX_FIELDS) return MTBLX_E_INVAL;
+  for (uint32_t f = 0; f < spec->nfields; ++f)
+    if (spec->op[f] > MTBLX_REDUCE_MAX) return MTBLX_E_INVAL;
+  return MTBLX_OK;
+}
+
+extern "C" int mtblx_scan_reduce(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
+                                 uint64_t index_off, uint64_t index_len, const uint64_t* tab_start,
+                                 const uint64_t* tab_doff, const uint64_t* tab_dlen, const int32_t* tab_st,
+                                 uint32_t ntab, const uint8_t* dec, const int32_t* type, const uint8_t* keys,
+                                 const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
+                                 const uint64_t* max_records, uint32_t max_blocks, uint32_t nq, mtblx_scan_result* res,
+                                 uint64_t* totals, void* ws, size_t wsb, const mtblx_reduce* spec, uint64_t* fields,
+                                 uint64_t* nbad, void* stream) {
+  if (!fields || !nbad || ((reinterpret_cast<uintptr_t>(fields) | reinterpret_cast<uintptr_t>(nbad)) & 7u))
+    return MTBLX_E_INVAL;
+  int c = spec_check(spec);
+  if (c != MTBLX_OK) return c;
+  c = scan_plan_check(file, version, tab_start, tab_doff, tab_dlen, tab_st, ntab, dec, type, keys, key_end, keys2,
+                      key2_end, nq, res, totals, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  if (nq == 0) return MTBLX_OK;
+  return mtblx_scan_impl_reduce(file, file_len, version, verify, index_off, index_len, tab_start, tab_doff, tab_dlen,
+                                tab_st, ntab, dec, type, keys, key_end, keys2, key2_end, max_records, max_blocks, nq,
+                                res, totals, ws, spec, fields, nbad, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mtblx_reduce_segments(const mtblx_records* recs, const uint64_t* seg_lo, const uint64_t* seg_hi,
+                                     uint32_t nseg, const mtblx_reduce* spec, uint64_t* fields, uint64_t* nbad,
+                                     uint32_t* flags, void* stream) {
+  if (!fields || !nbad || !flags) return MTBLX_E_INVAL;
+  // the kernels load and update these as aligned words
+  if (((reinterpret_cast<uintptr_t>(fields) | reinterpret_cast<uintptr_t>(nbad) | reinterpret_cast<uintptr_t>(seg_lo) |
+        reinterpret_cast<uintptr_t>(seg_hi)) & 7u) || (reinterpret_cast<uintptr_t>(flags) & 3u))
+    return MTBLX_E_INVAL;
+  if (nseg > MTBLX_REDUCE_MAX_SEGMENTS) return MTBLX_E_INVAL;
+  const int c = spec_check(spec);
+  if (c != MTBLX_OK) return c;
+  if (!recs || recs->n >= MTBLX_MERGE_MAX_RECORDS) return MTBLX_E_INVAL;
+  if (recs->n && (!recs->val_end || (reinterpret_cast<uintptr_t>(recs->val_end) & 7u)))
+    return MTBLX_E_INVAL;   // vals may be NULL where every value is empty
+  if (nseg && (!seg_lo || !seg_hi)) return MTBLX_E_INVAL;
+  if (nseg == 0) return MTBLX_OK;
+  return mtblx_reduce_seg_impl(recs, seg_lo, seg_hi, nseg, spec, fields, nbad, flags,
+                               reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- bounds-checked diagnostic build only (csrc/bounds.h, Makefile target `bounds`) ----

@@ -28,6 +28,7 @@
 // output slots are unaligned and written with plain (packed) stores, never with atomics.
 #pragma once
 #include "merge_dev.h"
+#include "reduce_ops.h"   // RSpec, the op table, Seg and its join: shared with reduce_seg.hip and scan.hip
 
 namespace {
 
@@ -35,56 +36,6 @@ constexpr int kEdgeWords = kReduceEdgeWords;   // per tile: lead[8], trail[8], m
 // meta: bit 0 the tile has a head, bit 2 the trail's group goes on past the tile, bit 3 trail bad,
 // bits 32.. the record index of the trail's head.  lead bad: a value of another length in the lead
 enum { E_LEAD = 0, E_TRAIL = 8, E_META = 16, E_LBAD = 17 };
-
-struct RSpec {       // travels in the kernel arguments; op of field f = (ops >> 8 f) & 0xFF, so no
-  uint64_t ops;      // kernel indexes an array with a run-time field number
-};
-
-__device__ __forceinline__ uint32_t r_op(const RSpec& sp, int f) { return (uint32_t)(sp.ops >> (8 * f)) & 0xFFu; }
-__device__ __forceinline__ uint64_t r_ident(uint32_t op) { return op == MTBLX_REDUCE_MIN ? ~0ull : 0ull; }
-__device__ __forceinline__ uint64_t r_apply(uint32_t op, uint64_t a, uint64_t b) {
-  return op == MTBLX_REDUCE_SUM ? a + b : op == MTBLX_REDUCE_MIN ? (a < b ? a : b) : (a > b ? a : b);
-}
-
-// a run of records: v = the fields reduced since the run's last head (or over the whole run if it
-// has none), fl bit 0 = the run has a head, bit 1 = a bad value since that head, hidx = that head
-template <int F>
-struct Seg {
-  uint64_t v[F];
-  uint32_t fl, hidx;
-};
-
-template <int F>
-__device__ __forceinline__ Seg<F> seg_ident(const RSpec& sp) {
-  Seg<F> r;
-#pragma unroll
-  for (int f = 0; f < F; ++f) r.v[f] = r_ident(r_op(sp, f));
-  r.fl = 0;
-  r.hidx = 0;
-  return r;
-}
-
-// run a followed by run b
-template <int F>
-__device__ __forceinline__ Seg<F> seg_join(const RSpec& sp, const Seg<F>& a, const Seg<F>& b) {
-  const bool cut = b.fl & 1u;
-  Seg<F> r;
-#pragma unroll
-  for (int f = 0; f < F; ++f) r.v[f] = cut ? b.v[f] : r_apply(r_op(sp, f), a.v[f], b.v[f]);
-  r.fl = cut ? b.fl : (a.fl | b.fl);
-  r.hidx = cut ? b.hidx : a.hidx;
-  return r;
-}
-
-template <int F>
-__device__ __forceinline__ Seg<F> seg_shfl_up(const Seg<F>& x, int o) {
-  Seg<F> r;
-#pragma unroll
-  for (int f = 0; f < F; ++f) r.v[f] = __shfl_up((unsigned long long)x.v[f], o, 64);
-  r.fl = __shfl_up(x.fl, o, 64);
-  r.hidx = __shfl_up(x.hidx, o, 64);
-  return r;
-}
 
 // the group's W bytes at vals + off, if they fit; -> false on overflow
 template <int F>
@@ -273,17 +224,6 @@ __global__ void __launch_bounds__(kThreads) k_reduce_edges(const uint64_t* hdr, 
 }
 
 // ---- host side ----
-// -> false if the spec is not one (mtblx_api.cpp has checked it already)
-inline bool reduce_spec(const mtblx_reduce* spec, RSpec* sp) {
-  if (!spec || spec->nfields < 1 || spec->nfields > MTBLX_REDUCE_MAX_FIELDS) return false;
-  sp->ops = 0;
-  for (uint32_t f = 0; f < spec->nfields; ++f) {
-    if (spec->op[f] > MTBLX_REDUCE_MAX) return false;
-    sp->ops |= (uint64_t)spec->op[f] << (8 * f);
-  }
-  return true;
-}
-
 template <int F>
 void reduce_launch_f(const SrcTab& t, uint8_t* w, const Layout& L, const Handle* hf, const mtblx_merged& o, RSpec sp,
                      uint32_t n, uint64_t planned, hipStream_t s) {

@@ -27,6 +27,7 @@
 #include "crc_dev.h"
 #include "mtblx.h"
 #include "reader_dev.h"
+#include "reduce_ops.h"
 
 namespace mtblx_rd {
 
@@ -105,11 +106,35 @@ __device__ __forceinline__ int seek2(const Blk& b, It& it, It& jt, const Targets
   }
 }
 
+// the reducing walk's extra arguments (mtblx_scan_reduce): lane f < nf keeps field f's accumulator
+struct Red {
+  RSpec sp;
+  uint32_t nf;
+  uint64_t* fields;   // [nq * nf]
+  uint64_t* nbad;     // [nq]
+};
+
+// what a lane of the reducing walk carries: its op, its accumulator, the values of another length
+template <bool ON>
+struct RAcc {};
+template <>
+struct RAcc<true> {
+  uint32_t op = 0;
+  uint64_t acc = 0, bad = 0;
+};
+__device__ __forceinline__ const Red& red_of(const Red& r) { return r; }
+
+// The plan walk, a kernel template on its trailing arguments.  k_scan_plan<> is the plan as it
+// always was, with the same kernel arguments.  k_scan_plan<Red> (mtblx_scan_reduce) also folds every
+// accepted record whose value is 8 * nf bytes long into the lanes' accumulators where the walk
+// counts it, and counts the others in nbad.
+template <class... RD>
 __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
                                                    uint64_t idx_off, uint64_t idx_len, DecTab tab, const int32_t* type,
                                                    const uint8_t* qkeys, const uint64_t* qend, const uint8_t* qkeys2,
                                                    const uint64_t* qend2, const uint64_t* maxrec, uint32_t max_blocks,
-                                                   uint32_t nq, mtblx_scan_result* wres, Land* land) {
+                                                   uint32_t nq, mtblx_scan_result* wres, Land* land, RD... red) {
+  constexpr bool RED = sizeof...(RD) != 0;
   __shared__ uint32_t T[256];
   for (int i = threadIdx.x; i < 256; i += blockDim.x) T[i] = mtblx_crc::kTab.byte[i];
   __syncthreads();
@@ -136,6 +161,11 @@ __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t
     Land ld{};
     Blk ib{}, db{};
     It ii{}, di{}, dj{};
+    RAcc<RED> ra;
+    if constexpr (RED) {
+      ra.op = r_op(red_of(red...).sp, lane & 7);
+      ra.acc = r_ident(ra.op);
+    }
     do {
       if (block_init(file + idx_off, idx_len, ib) != 0) break;   // the Reader's index block
       if (iter_init(ib, ii) != R_OK) break;
@@ -195,6 +225,16 @@ __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t
         ++nrec;
         kb += di.klen;
         vb += di.vlen;
+        if constexpr (RED) {   // the value is db.d + [voff, voff + vlen), inside the block (checked above)
+          const Red& rd = red_of(red...);
+          if (di.vlen != 8ull * rd.nf) {
+            ++ra.bad;
+          } else if ((uint32_t)lane < rd.nf) {
+            const uint8_t* vp = db.d + di.voff + 8u * (uint32_t)lane;   // any alignment
+            MTBLX_CHK(vp, 8);
+            ra.acc = r_apply(ra.op, ra.acc, *reinterpret_cast<const u64u*>(vp));
+          }
+        }
       }
     } while (false);
     mtblx_scan_result R{};
@@ -209,6 +249,17 @@ __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t
     MTBLX_CHK(wres + q, sizeof(R));
     MTBLX_CHK(land + q, sizeof(ld));
     if (lane == 0) { wres[q] = R; land[q] = ld; }
+    if constexpr (RED) {   // not OK: zero fields and zero nbad, as the counts
+      const bool ok = st == MTBLX_SCAN_OK;
+      const Red& rd = red_of(red...);
+      if ((uint32_t)lane < rd.nf) {
+        uint64_t* fp = rd.fields + (uint64_t)q * rd.nf + (uint32_t)lane;
+        MTBLX_CHK(fp, 8);
+        *fp = ok ? ra.acc : 0;
+      }
+      MTBLX_CHK(rd.nbad + q, 8);
+      if (lane == 0) rd.nbad[q] = ok ? ra.bad : 0;
+    }
   }
 }
 
@@ -402,6 +453,15 @@ __global__ void __launch_bounds__(64) k_scan_emit(const uint8_t* file, uint64_t 
 
 extern "C" size_t mtblx_scan_impl_ws_bytes(uint32_t nq) { return mtblx_rd::layout(nq).total; }
 
+extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
+                                      uint64_t index_off, uint64_t index_len, const uint64_t* tab_start,
+                                      const uint64_t* tab_doff, const uint64_t* tab_dlen, const int32_t* tab_st,
+                                      uint32_t ntab_in, const uint8_t* dec, const int32_t* type, const uint8_t* keys,
+                                      const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
+                                      const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
+                                      mtblx_scan_result* res, uint64_t* totals, void* ws, const mtblx_reduce* spec,
+                                      uint64_t* fields, uint64_t* nbad, hipStream_t s);
+
 // arguments already checked (mtblx_api.cpp): ws 256-byte aligned and large enough, every type in 0..3
 extern "C" int mtblx_scan_impl_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
                                     uint64_t index_off, uint64_t index_len, const uint64_t* tab_start,
@@ -409,7 +469,28 @@ extern "C" int mtblx_scan_impl_plan(const uint8_t* file, uint64_t file_len, uint
                                     uint32_t ntab_in, const uint8_t* dec, const int32_t* type, const uint8_t* keys, const uint64_t* key_end, const uint8_t* keys2,
                                     const uint64_t* key2_end, const uint64_t* max_records, uint32_t max_blocks,
                                     uint32_t nq, mtblx_scan_result* res, uint64_t* totals, void* ws, hipStream_t s) {
+  return mtblx_scan_impl_reduce(file, file_len, version, verify, index_off, index_len, tab_start, tab_doff, tab_dlen,
+                                tab_st, ntab_in, dec, type, keys, key_end, keys2, key2_end, max_records, max_blocks, nq,
+                                res, totals, ws, nullptr, nullptr, nullptr, s);
+}
+
+// spec == NULL: the plan alone.  Else k_scan_plan<Red> takes k_scan_plan<>'s place and fills fields / nbad.
+extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
+                                      uint64_t index_off, uint64_t index_len, const uint64_t* tab_start,
+                                      const uint64_t* tab_doff, const uint64_t* tab_dlen, const int32_t* tab_st,
+                                      uint32_t ntab_in, const uint8_t* dec, const int32_t* type, const uint8_t* keys,
+                                      const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
+                                      const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
+                                      mtblx_scan_result* res, uint64_t* totals, void* ws, const mtblx_reduce* spec,
+                                      uint64_t* fields, uint64_t* nbad, hipStream_t s) {
   using namespace mtblx_rd;
+  Red rd{};
+  if (spec) {
+    if (!reduce_spec(spec, &rd.sp)) return MTBLX_E_INVAL;
+    rd.nf = spec->nfields;
+    rd.fields = fields;
+    rd.nbad = nbad;
+  }
   const DecTab tab = dec ? DecTab{tab_start, tab_doff, tab_dlen, tab_st, ntab_in, dec}
                          : DecTab{nullptr, nullptr, nullptr, nullptr, 0u, nullptr};
   const Layout L = layout(nq);
@@ -423,12 +504,22 @@ extern "C" int mtblx_scan_impl_plan(const uint8_t* file, uint64_t file_len, uint
   const uint64_t need = ((uint64_t)nq + 3u) / 4u, cap = (uint64_t)mtblx_dev::cu_count() * 8u;
   const uint64_t ntab = tab.dec ? tab.n : 0;
   (void)ntab;   // read by the bounds-checked build only
-  MTBLX_LAUNCH((MTBLX_R(file, file_len), MTBLX_R(tab.start, 8ull * ntab), MTBLX_R(tab.doff, 8ull * ntab),
-                MTBLX_R(tab.dlen, 8ull * ntab), MTBLX_R(tab.st, 4ull * ntab), tab.dec, keys, MTBLX_R(key_end, 8ull * nq),
-                keys2, MTBLX_R(key2_end, 8ull * nq), MTBLX_R(max_records, 8ull * nq), MTBLX_R(w, L.total)),
-               k_scan_plan, dim3((unsigned)(need < cap ? need : cap)), dim3(256), 0, s, file, file_len, version, verify,
-               index_off, index_len, tab, dtype, keys, key_end, keys2, key2_end, max_records, max_blocks, nq, wres,
-               land);
+  if (!spec)
+    MTBLX_LAUNCH((MTBLX_R(file, file_len), MTBLX_R(tab.start, 8ull * ntab), MTBLX_R(tab.doff, 8ull * ntab),
+                  MTBLX_R(tab.dlen, 8ull * ntab), MTBLX_R(tab.st, 4ull * ntab), tab.dec, keys,
+                  MTBLX_R(key_end, 8ull * nq), keys2, MTBLX_R(key2_end, 8ull * nq), MTBLX_R(max_records, 8ull * nq),
+                  MTBLX_R(w, L.total)),
+                 k_scan_plan<>, dim3((unsigned)(need < cap ? need : cap)), dim3(256), 0, s, file, file_len, version,
+                 verify, index_off, index_len, tab, dtype, keys, key_end, keys2, key2_end, max_records, max_blocks, nq,
+                 wres, land);
+  else
+    MTBLX_LAUNCH((MTBLX_R(file, file_len), MTBLX_R(tab.start, 8ull * ntab), MTBLX_R(tab.doff, 8ull * ntab),
+                  MTBLX_R(tab.dlen, 8ull * ntab), MTBLX_R(tab.st, 4ull * ntab), tab.dec, keys,
+                  MTBLX_R(key_end, 8ull * nq), keys2, MTBLX_R(key2_end, 8ull * nq), MTBLX_R(max_records, 8ull * nq),
+                  MTBLX_R(w, L.total), MTBLX_R(fields, 8ull * nq * rd.nf), MTBLX_R(nbad, 8ull * nq)),
+                 k_scan_plan<Red>, dim3((unsigned)(need < cap ? need : cap)), dim3(256), 0, s, file, file_len, version,
+                 verify, index_off, index_len, tab, dtype, keys, key_end, keys2, key2_end, max_records, max_blocks, nq,
+                 wres, land, rd);
   MTBLX_LAUNCH((MTBLX_R(w, L.total), MTBLX_R(res, sizeof(mtblx_scan_result) * (uint64_t)nq)), k_scan_offsets, dim3(1),
                dim3(1024), 0, s, wres, res, nq, hdr, planned_mark(nq));
   if (hipGetLastError() != hipSuccess) return MTBLX_E_HIP;

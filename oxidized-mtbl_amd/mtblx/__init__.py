@@ -11,7 +11,7 @@ Package layout
   reduce.py   Reduce / MergeError: u64 sum / min / max merge functions evaluated on the device (csrc/reduce_dev.h)
 """
 from ._lib import EXPORTS, LIB_PATH, lib  # noqa: F401
-from .reduce import MergeError, Reduce  # noqa: F401
+from .reduce import MergeError, Reduce, ReduceBatch, reduce_segments  # noqa: F401
 from .writer import CompressionType, OutOfOrderKey, Writer, WriterBuilder  # noqa: F401
 
 

@@ -50,6 +50,7 @@ EXPORTS = [
     "mtblx_snappy_compress_workspace_bytes", "mtblx_snappy_slots", "mtblx_snappy_compress_dev", "mtblx_frame_blocks",
     "mtblx_encode_index_c",
     "mtblx_scan_workspace_bytes", "mtblx_scan_plan", "mtblx_scan_emit",
+    "mtblx_scan_reduce", "mtblx_reduce_segments", "mtblx_reduce_seg_tile",
     "mtblx_stage_workspace_bytes", "mtblx_stage_plan", "mtblx_stage_emit", "mtblx_scan_touch", "mtblx_bitmap_compact",
     "mtblx_table_gather", "mtblx_dir_ascends",
 ]
@@ -62,6 +63,9 @@ MERGE_MAX_SEGMENTS = 1 << 24                   # MTBLX_MERGE_MAX_SEGMENTS: segme
 MERGE_BADSEG = 4                               # totals[5] of mtblx_merge_seg_plan: a bad seg_off array
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)  # mtblx_reduce.op
 REDUCE_MAX_FIELDS = 8
+REDUCE_BADSEG = 8                              # *flags of mtblx_reduce_segments: a bad segment array
+REDUCE_MAX_SEGMENTS = 0xFFFFFF00               # MTBLX_REDUCE_MAX_SEGMENTS: nseg of mtblx_reduce_segments
+REDUCE_SEG_TILE = 1024                         # MTBLX_REDUCE_SEG_TILE: records per workgroup of mtblx_reduce_segments
 SORT_TILE = 1024                               # MTBLX_SORT_TILE: handles per tile-sorted run of mtblx_sort_plan
 PLAN_OUT_OF_ORDER, PLAN_PANIC, PLAN_TOO_LONG = 1, 2, 4
 SCAN_OK, SCAN_LARGE, SCAN_FALLBACK = range(3)  # mtblx_scan_result.status
@@ -343,6 +347,13 @@ def lib() -> C.CDLL:
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
             C.c_void_p, u64p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.mtblx_scan_plan.restype = C.c_int
+        L.mtblx_scan_reduce.argtypes = L.mtblx_scan_plan.argtypes[:-1] + [C.POINTER(ReduceSpec), C.c_void_p,
+                                                                          C.c_void_p, C.c_void_p]
+        L.mtblx_scan_reduce.restype = C.c_int
+        L.mtblx_reduce_segments.argtypes = [C.POINTER(Records), C.c_void_p, C.c_void_p, C.c_uint32,
+                                            C.POINTER(ReduceSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mtblx_reduce_segments.restype = C.c_int
+        L.mtblx_reduce_seg_tile.restype = C.c_uint32
         L.mtblx_scan_emit.argtypes = _file + [C.c_uint64, C.c_uint64] + _tab + [
             C.c_uint32, C.POINTER(Scanned), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mtblx_scan_emit.restype = C.c_int

@@ -35,7 +35,7 @@ import torch
 
 from . import _lib, codec, encode
 from .encode import DeviceRecords
-from .reduce import MergeError, Reduce, as_reduce, check_merge  # noqa: F401
+from .reduce import MergeError, Reduce, ReduceBatch, as_reduce, check_merge, reduce_segments  # noqa: F401
 from .writer import CompressionType
 
 MODES = {"groups": _lib.MERGE_GROUPS, "concat": _lib.MERGE_CONCAT, "first": _lib.MERGE_FIRST,
@@ -626,3 +626,38 @@ class Merger:
     def get_batch(self, keys, max_blocks: int = 64, stream=None) -> MergedScanBatch:
         """the merged value of every key: scan_batch of ("get", k); count[q] is 0 or 1"""
         return self.scan_batch([("get", bytes(k)) for k in keys], max_blocks, None, stream)
+
+    def reduce_batch(self, queries, reduce=None, max_blocks: int = 64, max_records=None, stream=None) -> ReduceBatch:
+        """Reader.reduce_batch over the merged view: per query, `reduce` folded (Reduce.fold) over the
+        merged values scan_batch reports for it.  scan_batch runs as it stands -- the Merger's own merge
+        function (a built-in name or a Reduce) joins each key's values -- and one reduce_segments over
+        the segments [grp_off[q], grp_off[q] + count[q]) of the merged buffers folds them; a query some
+        source handed back is reduced from its own device records.  `reduce=None` takes the Merger's
+        merge function when it is a Reduce.  A callable merge function is refused: the batch then holds
+        groups, not values.  Everything runs on `stream` (default: Merger(stream=), else the current
+        stream)."""
+        if callable(self.merge):
+            raise ValueError("reduce_batch: a callable merge function leaves groups, not merged values")
+        red = as_reduce(reduce if reduce is not None else self.merge)
+        if red is None:
+            raise ValueError("reduce_batch: pass a Reduce (the Merger's merge function is not one)" if reduce is None
+                             else f"reduce_batch: {reduce!r} is not a Reduce")
+        mb = self.scan_batch(queries, max_blocks, max_records, stream)   # checks the queries before any source is touched
+        s = mb._stream
+        with torch.cuda.stream(s):
+            lo = mb.grp_off[:-1].contiguous()
+            cnt = mb._count.copy()
+            cnt[sorted(mb._served)] = 0   # count[q] of a handed-back query counts merge_all's answer, not its slot
+            fields, nbad = reduce_segments(DeviceRecords(mb.keys, mb.key_end, mb.vals, mb.val_end), lo,
+                                           lo + torch.from_numpy(cnt).to(lo.device), red, s)
+            nrec = mb.count.clone()
+            for q, r in mb._served.items():   # its slot in the buffers holds what the kernels left of it
+                n = int(r.key_end.numel())
+                f, nb = reduce_segments(r, [0], [n], red, s)
+                fields[q] = f[0]
+                nbad[q] = nb[0]
+            status = torch.zeros(mb.nq, dtype=torch.int32, device=nrec.device)
+            if mb._served:
+                status[torch.tensor(sorted(mb._served), dtype=torch.int64, device=nrec.device)] = _lib.SCAN_FALLBACK
+            ends = {q: (0, "None") for q in mb._served}   # a source's error has raised in scan_batch
+            return ReduceBatch(red, fields, nrec, nbad, status, ends, mb.n_large, mb.n_fallback, s)

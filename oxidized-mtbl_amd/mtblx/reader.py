@@ -895,9 +895,10 @@ class Reader:
         return iterator.bulk(self, "range", bytes(start), bytes(end))
 
     # ------------------------------------------------------------------ batched scans
-    def _scan_plan(self, queries, max_blocks, max_records, stream):
+    def _scan_plan(self, queries, max_blocks, max_records, stream, reduce=None):
         """mtblx_scan_plan over `queries` -> (res uint8 [nq * 64] device, totals, workspace, per-query
-        limits, table arguments)"""
+        limits, table arguments).  With a Reduce the call is mtblx_scan_reduce and the tuple ends with
+        (fields int64 [nq, F], nbad int64 [nq])."""
         from . import iterator
         dev = self.file.device
         nq = len(queries)
@@ -949,15 +950,24 @@ class Reader:
             tab = (C.c_void_p(ts.data_ptr()), C.c_void_p(tdo.data_ptr()), C.c_void_p(tdl.data_ptr()),
                    C.c_void_p(tst.data_ptr()), ntab, C.c_void_p(dec.data_ptr()))
         totals = (C.c_uint64 * 4)()
-        rc = L.mtblx_scan_plan(C.c_void_p(self.file.data_ptr()), self.len, self.version, 1 if self.verify else 0,
-                               self.index_off, self.index_len, *tab, C.c_void_p(types.ctypes.data),
-                               C.c_void_p(kb.data_ptr()), C.c_void_p(ke.data_ptr()), C.c_void_p(k2b.data_ptr()),
-                               C.c_void_p(k2e.data_ptr()), C.c_void_p(mr.data_ptr()) if mr is not None else None,
-                               max_blocks, nq, C.c_void_p(res.data_ptr()), totals, C.c_void_p(ws.data_ptr()), wsb,
-                               C.c_void_p(codec._stream_handle(stream)))
+        args = (C.c_void_p(self.file.data_ptr()), self.len, self.version, 1 if self.verify else 0,
+                self.index_off, self.index_len, *tab, C.c_void_p(types.ctypes.data),
+                C.c_void_p(kb.data_ptr()), C.c_void_p(ke.data_ptr()), C.c_void_p(k2b.data_ptr()),
+                C.c_void_p(k2e.data_ptr()), C.c_void_p(mr.data_ptr()) if mr is not None else None,
+                max_blocks, nq, C.c_void_p(res.data_ptr()), totals, C.c_void_p(ws.data_ptr()), wsb)
+        if reduce is None:
+            rc = L.mtblx_scan_plan(*args, C.c_void_p(codec._stream_handle(stream)))
+            if rc != 0:
+                raise RuntimeError(f"mtblx_scan_plan failed: {rc}")
+            return res, [int(x) for x in totals], ws, wsb, limits, tab, keep
+        spec = reduce.cstruct()
+        fields = torch.zeros((max(nq, 1), len(reduce.ops)), dtype=torch.int64, device=dev)
+        nbad = torch.zeros(max(nq, 1), dtype=torch.int64, device=dev)
+        rc = L.mtblx_scan_reduce(*args, C.byref(spec), C.c_void_p(fields.data_ptr()), C.c_void_p(nbad.data_ptr()),
+                                 C.c_void_p(codec._stream_handle(stream)))
         if rc != 0:
-            raise RuntimeError(f"mtblx_scan_plan failed: {rc}")
-        return res, [int(x) for x in totals], ws, wsb, limits, tab, keep
+            raise RuntimeError(f"mtblx_scan_reduce failed: {rc}")
+        return res, [int(x) for x in totals], ws, wsb, limits, tab, keep, (fields[:nq], nbad[:nq])
 
     def count_batch(self, queries, max_blocks: int = 64, stream=None):
         """The plan of scan_batch alone: (status int32, nrec, key_bytes, val_bytes int64) [nq] on the
@@ -983,22 +993,26 @@ class Reader:
         with torch.cuda.stream(stream):
             return self._scan_batch(list(queries), max_blocks, max_records, stream)
 
-    def _scan_batch(self, queries, max_blocks, max_records, stream) -> "ScanBatch":
+    def _scan_limited(self, query, m, stream) -> Scan:
+        """one query of a batch through the seek path (iterator.bulk), cut at its limit `m`"""
         from . import iterator
+        kind = query[0]
+        s = iterator.bulk(self, kind, bytes(query[1]), bytes(query[2]) if kind == "range" else b"")
+        if kind == "get":
+            m = 1 if m is None else min(m, 1)
+        if m is None or s.nrec < m or (m == 0 and s.end != END_NONE):
+            s.stream = stream
+            return s
+        p = iterator._cut_part((s.keys, s.vals, s.key_end, s.val_end, s.nrec), m)
+        return Scan(END_NONE, "None", m, p[0], p[1], p[2], p[3], stream)
+
+    def _scan_batch(self, queries, max_blocks, max_records, stream) -> "ScanBatch":
         dev = self.file.device
         queries = list(queries)
         nq = len(queries)
 
         def limited(q, m):
-            kind = queries[q][0]
-            s = iterator.bulk(self, kind, bytes(queries[q][1]), bytes(queries[q][2]) if kind == "range" else b"")
-            if kind == "get":
-                m = 1 if m is None else min(m, 1)
-            if m is None or s.nrec < m or (m == 0 and s.end != END_NONE):
-                s.stream = stream
-                return s
-            p = iterator._cut_part((s.keys, s.vals, s.key_end, s.val_end, s.nrec), m)
-            return Scan(END_NONE, "None", m, p[0], p[1], p[2], p[3], stream)
+            return self._scan_limited(queries[q], m, stream)
 
         z8 = torch.zeros(0, dtype=torch.uint8, device=dev)
         z64 = torch.zeros(0, dtype=torch.int64, device=dev)
@@ -1038,6 +1052,57 @@ class Reader:
         status = res.view(torch.int32).view(-1, 16)[:nq, 0]
         served = {int(q): limited(int(q), limits[int(q)]) for q in np.nonzero(host["status"] != _lib.SCAN_OK)[0]}
         return ScanBatch(nq, keys, vals, key_end, val_end, rec_off, status, host, served, stream)
+
+    def reduce_batch(self, queries, reduce, max_blocks: int = 64, max_records=None, stream=None) -> "ReduceBatch":
+        """scan_batch that aggregates instead of returning records: per query, `reduce` (a Reduce or a
+        shorthand name) folded over the values of the records scan_batch would report (same stop rules,
+        same `max_records`, ("get", k) at most one record), as Reduce.fold defines it.  One
+        mtblx_scan_reduce -- the plan walk reads each value where it lies, no key or value is
+        materialised -- and one read-back; the answer is 8 * F + 16 bytes per query.  A query the walk
+        hands back (SCAN_LARGE, SCAN_FALLBACK) and every query of a reader with an irregular index is
+        answered by iterator.bulk() with the limit applied and its device records are reduced by
+        reduce_segments: no record is copied to the host.  Everything runs on `stream` (default: the
+        current stream), which the call synchronises."""
+        from .reduce import as_reduce
+        red = as_reduce(reduce)
+        if red is None:
+            raise ValueError(f"reduce_batch: {reduce!r} is not a Reduce")
+        stream = self._s(stream)
+        with torch.cuda.stream(stream):
+            return self._reduce_batch(list(queries), red, max_blocks, max_records, stream)
+
+    def _reduce_batch(self, queries, red, max_blocks, max_records, stream) -> "ReduceBatch":
+        from .encode import DeviceRecords
+        from .reduce import ReduceBatch, _signed, reduce_segments
+        dev = self.file.device
+        nq = len(queries)
+        if nq == 0 or not self.index_regular():
+            from .merger import check_queries
+            queries, limits = check_queries(queries, max_records)   # the kernel path: _scan_plan checks them
+            fields = torch.tensor(_signed(red.identities()), dtype=torch.int64, device=dev).repeat(nq, 1)
+            nbad = torch.zeros(nq, dtype=torch.int64, device=dev)
+            nrec = torch.zeros(nq, dtype=torch.int64, device=dev)
+            status = torch.full((nq,), _lib.SCAN_FALLBACK, dtype=torch.int32, device=dev)
+            back, n_large, n_fallback = range(nq), 0, nq
+        else:
+            res, _, _, _, limits, _, _, (fields, nbad) = self._scan_plan(queries, max_blocks, max_records, stream, red)
+            # the one read-back: mtblx_scan_reduce has synchronised `stream`
+            host = np.frombuffer(res.cpu().numpy().tobytes(), np.dtype(_lib.ScanResult))[:nq]
+            nrec = res.view(torch.int64).view(-1, 8)[:nq, 1].clone()
+            status = res.view(torch.int32).view(-1, 16)[:nq, 0].clone()
+            back = [int(q) for q in np.nonzero(host["status"] != _lib.SCAN_OK)[0]]
+            n_large = int((host["status"] == _lib.SCAN_LARGE).sum())
+            n_fallback = int((host["status"] == _lib.SCAN_FALLBACK).sum())
+        ends = {}
+        for q in back:   # the seek path's answer stays on the device: one segment over its records
+            sc = self._scan_limited(queries[q], limits[q], stream)
+            n = sc.nrec
+            f, nb = reduce_segments(DeviceRecords(sc.keys, sc.key_end[:n], sc.vals, sc.val_end[:n]), [0], [n], red, stream)
+            fields[q] = f[0]
+            nbad[q] = nb[0]
+            nrec[q] = n
+            ends[q] = (sc.end, sc.err)
+        return ReduceBatch(red, fields, nrec, nbad, status, ends, n_large, n_fallback, stream)
 
     def into_iter(self, kind: str = "iter", key: bytes = b"", key2: bytes = b""):
         """the stateful ReaderIntoIter (next() / seek()), see iterator.ReaderIntoIter"""

@@ -10,6 +10,10 @@ on the device (mtblx_merge_emit_reduce / mtblx_sort_emit_reduce) and no record r
 It is not callable on purpose: a callable merge function is the host path.  ``Reduce.host`` is the
 same function on the host, for documentation and A/B runs.
 
+Aggregating scans (include/mtblx.h "Aggregating scans") fold the same spec over all the records a
+query matches: ``Reduce.fold`` is their definition on the host, ``reduce_segments`` the device
+primitive, ``ReduceBatch`` the result of Reader.reduce_batch / Merger.reduce_batch.
+
 As the reference never calls its merge function for a group of one (src/merger.rs:200-201,
 src/sorter.rs:166-167), a value alone in its group comes out unchanged whatever its length; in a
 group of two or more every value must be exactly 8 * nfields bytes long, else MergeError.
@@ -74,6 +78,28 @@ class Reduce:
         return bytes(out)
 
 
+    def identities(self):
+        """what a field is over nothing: 0 for "sum" and "max", 2^64 - 1 for "min" """
+        return tuple(_MASK if op == "min" else 0 for op in self.ops)
+
+    def fold(self, values):
+        """The aggregating scans' semantics on the host: -> (fields, nrec, nbad).  nrec = len(values);
+        nbad = the values that are not exactly `width` bytes long, left out and counted; fields[f] =
+        op[f] over field f of the others (unsigned, "sum" mod 2^64), the op's identity over nothing."""
+        w = self.width
+        acc = list(self.identities())
+        nrec = nbad = 0
+        for v in values:
+            nrec += 1
+            if len(v) != w:
+                nbad += 1
+                continue
+            for f, op in enumerate(self.ops):
+                x = int.from_bytes(v[8 * f: 8 * f + 8], "little")
+                acc[f] = (acc[f] + x) & _MASK if op == "sum" else min(acc[f], x) if op == "min" else max(acc[f], x)
+        return tuple(acc), nrec, nbad
+
+
 def as_reduce(merge):
     """a Reduce or one of its shorthand names -> the Reduce; anything else -> None"""
     if isinstance(merge, Reduce):
@@ -91,3 +117,112 @@ def check_merge(merge):
     if not callable(merge) and merge not in ("concat", "first", "last"):
         raise ValueError(f"merge: {merge!r}")
     return merge
+
+
+def reduce_segments(records, seg_lo, seg_hi, reduce, stream=None):
+    """mtblx_reduce_segments: `reduce` folded over segments of device records.  `records`: an
+    encode.DeviceRecords (only vals / val_end are read); segment s = records [seg_lo[s], seg_hi[s])
+    (device int64 [nseg], or anything torch.as_tensor takes), with seg_lo[s] <= seg_hi[s] <=
+    seg_lo[s + 1] and seg_hi[-1] <= n; records in no segment bring nothing.  -> device (fields int64
+    [nseg, F]: the u64 bit patterns, nbad int64 [nseg]); ValueError for a segment array that breaks
+    the rule.  Uploads, kernels and the flags' read-back run on `stream` (default: the current one)."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib, codec
+    red = as_reduce(reduce)
+    if red is None:
+        raise ValueError(f"reduce_segments: {reduce!r} is not a Reduce")
+    dev = records.val_end.device
+    s = codec._stream_of(stream, dev)
+    with torch.cuda.stream(s):
+        lo = torch.as_tensor(seg_lo, dtype=torch.int64, device=dev).contiguous()
+        hi = torch.as_tensor(seg_hi, dtype=torch.int64, device=dev).contiguous()
+        if lo.dim() != 1 or lo.shape != hi.shape:
+            raise ValueError("reduce_segments: seg_lo and seg_hi must be two 1-d arrays of one length")
+        nseg, nf = int(lo.numel()), len(red.ops)
+        fields = torch.tensor(_signed(red.identities()), dtype=torch.int64, device=dev).repeat(nseg, 1)
+        nbad = torch.zeros(nseg, dtype=torch.int64, device=dev)
+        if nseg == 0:
+            return fields, nbad
+        flags = torch.zeros(2, dtype=torch.int32, device=dev)
+        ve = records.val_end.contiguous()
+        rec = _lib.Records(0, 0, codec._u(records.vals), codec._u(ve), int(ve.numel()))
+        spec = red.cstruct()
+        rc = _lib.lib().mtblx_reduce_segments(C.byref(rec), C.c_void_p(lo.data_ptr()), C.c_void_p(hi.data_ptr()), nseg,
+                                              C.byref(spec), C.c_void_p(fields.data_ptr()),
+                                              C.c_void_p(nbad.data_ptr()), C.c_void_p(flags.data_ptr()),
+                                              C.c_void_p(codec._stream_handle(s)))
+        if rc != 0:
+            raise RuntimeError(f"mtblx_reduce_segments failed: {rc}")
+        fl = int(flags[0].item())   # on s, behind the kernels
+    if fl & _lib.REDUCE_BADSEG:
+        raise ValueError("reduce_segments: the segments must satisfy seg_lo[s] <= seg_hi[s] <= seg_lo[s + 1] "
+                         "and seg_hi[-1] <= n")
+    return fields, nbad
+
+
+def _signed(xs):
+    """u64 values as the int64 bit patterns the device tensors hold"""
+    return [x - (1 << 64) if x >> 63 else x for x in xs]
+
+
+class ReduceBatch:
+    """Reader.reduce_batch's / Merger.reduce_batch's result.  Device tensors: `fields` int64 [nq, F]
+    (the u64 bit patterns), `nrec` / `nbad` int64 [nq] (records yielded; those among them whose value
+    is not 8 * F bytes long, left out and counted), `status` int32 [nq] (SCAN_* of the scan walk).
+    A query the walk handed back (SCAN_LARGE, SCAN_FALLBACK, an irregular index) was answered by the
+    seek path and its device records reduced by reduce_segments: values(q) / value_bytes(q) give every
+    query's result, whichever path served it, and end(q) / err(q) how such a query's iteration ended
+    (Scan.end / Scan.err; END_NONE for a kernel-served query)."""
+
+    def __init__(self, reduce, fields, nrec, nbad, status, ends, n_large, n_fallback, stream=None):
+        self._stream = stream      # the stream of the batch: every host read goes through it
+        self.reduce = reduce
+        self.nq = int(nrec.numel())
+        self.fields, self.nrec, self.nbad, self.status = fields, nrec, nbad, status
+        self._ends = ends          # q -> (end, err) of the queries the seek path answered
+        self.n_large, self.n_fallback = n_large, n_fallback
+        self._host = None
+
+    def served_by_kernel(self, q: int) -> bool:
+        return q not in self._ends
+
+    def end(self, q: int) -> int:
+        return self._ends[q][0] if q in self._ends else 0   # reader.END_NONE
+
+    def err(self, q: int) -> str:
+        return self._ends[q][1] if q in self._ends else "None"
+
+    def _h(self):
+        if self._host is None:
+            import torch
+            with torch.cuda.stream(self._stream):   # one read-back, on the batch's stream
+                self._host = (self.fields.cpu().numpy().view("uint64"), self.nrec.cpu().numpy(),
+                              self.nbad.cpu().numpy())
+        return self._host
+
+    def values(self, q: int):
+        """query q's fields as a tuple of unsigned ints"""
+        return tuple(int(x) for x in self._h()[0][q])
+
+    def counts(self, q: int):
+        """(nrec, nbad) of query q"""
+        _, nr, nb = self._h()
+        return int(nr[q]), int(nb[q])
+
+    def value_bytes(self, q: int):
+        """the 8 * F bytes of query q's fields, or None when nothing was reduced"""
+        f, nr, nb = self._h()
+        if int(nr[q]) - int(nb[q]) == 0:
+            return None
+        return b"".join(int(x).to_bytes(8, "little") for x in f[q])
+
+    def check(self) -> None:
+        """MergeError if any query met a value that is not 8 * F bytes long"""
+        nb = self._h()[2]
+        if nb.any():
+            q = int(nb.nonzero()[0][0])
+            raise MergeError(f"reduce_batch: query {q} met {int(nb[q])} values that are not {self.reduce.width} "
+                             "bytes long")
