@@ -50,6 +50,17 @@ def _require_device():
     return L
 
 
+def u32_sum(t: torch.Tensor) -> int:
+    """the sum of a tensor of u32 lengths, which torch holds as int32 (a length of 2^31 or more
+    reads negative there)"""
+    return int((t.to(torch.int64) & 0xFFFFFFFF).sum().item()) if t.numel() else 0
+
+
+def u32_max(t: torch.Tensor) -> int:
+    """the largest of a tensor of u32 lengths held as int32 (max_blk_len of a batch); 0 when empty"""
+    return int((t.to(torch.int64) & 0xFFFFFFFF).max().item()) if t.numel() else 0
+
+
 def _u(t: torch.Tensor) -> int:
     return t.data_ptr() if t is not None and t.numel() else 0
 

@@ -159,7 +159,7 @@ class Encoded:
     def batch(self) -> codec.DeviceBatch:
         """the encoded blocks as a decode batch (mtblx_decode_blocks input)"""
         with torch.cuda.stream(self.stream):
-            ml = int(self.blk_len.max().item()) if self.blk_len.numel() else 0
+            ml = codec.u32_max(self.blk_len)
         return codec.DeviceBatch(self.out, self.blk_off, self.blk_len, ml)
 
 
@@ -210,6 +210,12 @@ def encode_blocks(recs: DeviceRecords, blk_rec: torch.Tensor, restart_interval: 
     s = codec._stream_of(stream, dev)
     bufs = EncodeBuffers(recs, int(blk_rec.numel()) - 1, device=dev, stream=s)
     return encode_into(recs, blk_rec, bufs, restart_interval, framed, s, plan)
+
+
+def stored_file_cap(stored_len: torch.Tensor, tail: int) -> int:
+    """capacity of a file of blocks stored with these (u32) content lengths: the contents, their
+    framing (varint64(len) <= 10 bytes + 4 of checksum per block) and `tail` bytes of index and footer"""
+    return codec.u32_sum(stored_len) + 14 * int(stored_len.numel()) + tail
 
 
 def write_file(recs: DeviceRecords, block_size: int = 8192, restart_interval: int = 16, stream=None,
@@ -263,11 +269,10 @@ def _write_file(recs: DeviceRecords, block_size: int, restart_interval: int, str
     tail = kbytes + 36 * nblk + 64 + 512
     if snappy and nblk:
         comp, cst = codec.snappy_compress(e.batch(), stream=stream)
-        stored = int(comp.src_len.sum().item())   # synchronises `stream`: the compressed sizes size the file
+        cap = stored_file_cap(comp.src_len, tail)   # synchronises `stream`: the compressed sizes size the file
         if bool((cst != 0).any()):
             raise RuntimeError("mtblx_snappy_compress_dev: a block did not fit its slot")
         del e, data   # the raw contents are not needed any more
-        cap = stored + 14 * nblk + tail   # framing: varint64(len) <= 10 bytes + 4 of checksum per block
         file = torch.empty(cap, dtype=torch.uint8, device=dev)
         off = torch.empty(nblk, dtype=torch.int64, device=dev)
         ftot = torch.zeros(2, dtype=torch.int64, device=dev)

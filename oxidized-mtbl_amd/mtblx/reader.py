@@ -293,7 +293,7 @@ class Reader:
         if not self.verify or i1 <= i0:
             return None
         off, ln, _ = self._framing()
-        batch = codec.DeviceBatch(self.file, off[i0:i1], ln[i0:i1], int(ln[i0:i1].max().item()))
+        batch = codec.DeviceBatch(self.file, off[i0:i1], ln[i0:i1], codec.u32_max(ln[i0:i1]))
         return codec.crc32c_blocks(batch, framed=True)[1]
 
     def _framing(self):
@@ -1268,7 +1268,7 @@ class Reader:
             bad = None
             if self.verify and n:
                 okl = torch.where(st == _lib.DIR_OK, ln, torch.zeros_like(ln))
-                batch = codec.DeviceBatch(self.file, off, okl, int(okl.max().item()))
+                batch = codec.DeviceBatch(self.file, off, okl, codec.u32_max(okl))
                 bad = codec.crc32c_blocks(batch, framed=True)[1]
         bad_dev = bad
         bad = bad.cpu().numpy() if bad is not None else np.zeros(n, np.uint8)
@@ -1287,7 +1287,7 @@ class Reader:
             where = (batch.data, uoff.astype(np.int64), uln.astype(np.int64))
         else:
             zerr = np.zeros(n, np.int32)
-            batch = codec.DeviceBatch(self.file, off, ln, int(ln.max().item()))
+            batch = codec.DeviceBatch(self.file, off, ln, codec.u32_max(ln))
             where = (self.file, off.cpu().numpy(), ln.cpu().numpy().view(np.uint32).astype(np.int64))
         data = codec.decode_blocks(batch)
         return dst, bad, zerr, data, where
