@@ -1324,7 +1324,7 @@ inline std::vector<Reader::Records> Reader::scan_batch(const std::vector<ScanQue
 // sources were added; the empty-key quirk of :182-186 is kept; an out-of-order source throws
 // UnsortedSource (the reference does not check).  More than MTBLX_MERGE_MAX_SOURCES sources are
 // merged in rounds with the same mode; a merge function is called once, at the end, and never
-// for a group of one (:200-207).  A MergeReduce (u64 sum / min / max per 8-byte field, mtblx.h
+// for a group of one (:200-207).  A MergeReduce (u64 sum / min / max per 8-byte or varint-coded field, mtblx.h
 // "Device merge functions") is evaluated on the device (mtblx_merge_emit_reduce), per round: the
 // ops are associative and commutative and a group of one passes through, so the rounds give the
 // bytes of one application; a group of two or more with a value of another length throws MergeError.
@@ -1332,14 +1332,23 @@ struct MergeConcat {};   // the group's values joined in source order (the refer
 struct MergeFirst {};    // the first-added source's value
 struct MergeLast {};     // the last-added source's value
 using MergeFn = std::function<Bytes(const Bytes& key, const std::vector<Bytes>& values)>;
-struct MergeReduce {     // one op (MTBLX_REDUCE_SUM / _MIN / _MAX) per little-endian u64 field, 1 to 8 of them
+enum class ReduceEncoding { U64le, Varint };   // 8 little-endian bytes per field | one LEB128 varint per field
+struct MergeReduce {     // one op (MTBLX_REDUCE_SUM / _MIN / _MAX) per u64 field, 1 to 8 of them
   std::vector<int> ops;
+  // Varint: a value is ops.size() varints back to back, the result re-encoded canonically (mtblx.h
+  // "Varint-coded values"); the default is the fixed-width value
+  ReduceEncoding encoding = ReduceEncoding::U64le;
   static MergeReduce sum() { return MergeReduce{{MTBLX_REDUCE_SUM}}; }
   static MergeReduce min() { return MergeReduce{{MTBLX_REDUCE_MIN}}; }
   static MergeReduce max() { return MergeReduce{{MTBLX_REDUCE_MAX}}; }
+  static MergeReduce varint(std::vector<int> ops) { return MergeReduce{std::move(ops), ReduceEncoding::Varint}; }
 };
 struct MergeError : std::runtime_error {   // the reference's Error::Merge
   MergeError() : std::runtime_error("merge: a group of two or more holds a value of another length than 8 * nfields") {}
+  explicit MergeError(const mtblx_reduce* rd)   // the text names the spec's encoding
+      : std::runtime_error(rd && (rd->op[0] & MTBLX_REDUCE_VARINT)
+                               ? "merge: a group of two or more holds a value that is not nfields varints back to back"
+                               : "merge: a group of two or more holds a value of another length than 8 * nfields") {}
 };
 struct UnsortedSource : std::runtime_error {
   UnsortedSource() : std::runtime_error("merge source out of order") {}
@@ -1357,25 +1366,50 @@ inline mtblx_reduce reduce_spec(const MergeReduce& r) {
   spec.nfields = static_cast<uint32_t>(r.ops.size());
   for (size_t f = 0; f < r.ops.size(); ++f) {
     if (r.ops[f] < MTBLX_REDUCE_SUM || r.ops[f] > MTBLX_REDUCE_MAX) throw std::invalid_argument("MergeReduce: unknown op");
-    spec.op[f] = static_cast<uint8_t>(r.ops[f]);
+    spec.op[f] = static_cast<uint8_t>(r.ops[f] | (r.encoding == ReduceEncoding::Varint ? MTBLX_REDUCE_VARINT : 0u));
   }
   return spec;
+}
+// the fields of a varint-coded value as varint_decode64 (src/varint.rs:78-97) reads them back to
+// back; -> false unless the value is exactly nf of them (mtblx.h "Varint-coded values")
+inline bool varint_fields(const Bytes& v, uint32_t nf, uint64_t* out) {
+  size_t p = 0;
+  for (uint32_t f = 0; f < nf; ++f) {
+    uint64_t x = 0;
+    bool done = false;
+    for (unsigned sh = 0; sh < 70 && p < v.size(); sh += 7) {
+      const uint8_t b = v[p++];
+      x |= static_cast<uint64_t>(b & 0x7f) << sh;
+      if (!(b & 0x80)) {
+        done = true;
+        break;
+      }
+    }
+    if (!done) return false;
+    out[f] = x;
+  }
+  return p == v.size();
 }
 // Reduce.fold of the Python surface: the aggregating scans' semantics on the host
 inline Reduced fold_host(const mtblx_reduce& spec, const Reader::Records& recs) {
   Reduced r;
-  for (uint32_t f = 0; f < spec.nfields; ++f) r.fields[f] = spec.op[f] == MTBLX_REDUCE_MIN ? ~0ull : 0ull;
+  const bool varint = spec.op[0] & MTBLX_REDUCE_VARINT;
+  for (uint32_t f = 0; f < spec.nfields; ++f)
+    r.fields[f] = (spec.op[f] & ~MTBLX_REDUCE_VARINT) == MTBLX_REDUCE_MIN ? ~0ull : 0ull;
   for (const auto& kv : recs) {
     ++r.nrec;
-    if (kv.second.size() != 8u * spec.nfields) {
+    uint64_t xs[MTBLX_REDUCE_MAX_FIELDS] = {};
+    if (varint ? !varint_fields(kv.second, spec.nfields, xs) : kv.second.size() != 8u * spec.nfields) {
       ++r.nbad;
       continue;
     }
     for (uint32_t f = 0; f < spec.nfields; ++f) {
-      uint64_t x = 0;
-      for (int b = 7; b >= 0; --b) x = (x << 8) | kv.second[8 * f + b];
+      uint64_t x = xs[f];
+      if (!varint)
+        for (int b = 7; b >= 0; --b) x = (x << 8) | kv.second[8 * f + b];
+      const unsigned op = spec.op[f] & ~MTBLX_REDUCE_VARINT;
       uint64_t& a = r.fields[f];
-      a = spec.op[f] == MTBLX_REDUCE_SUM ? a + x : spec.op[f] == MTBLX_REDUCE_MIN ? (x < a ? x : a) : (x > a ? x : a);
+      a = op == MTBLX_REDUCE_SUM ? a + x : op == MTBLX_REDUCE_MIN ? (x < a ? x : a) : (x > a ? x : a);
     }
   }
   return r;
@@ -1415,7 +1449,7 @@ inline HostGroups merge_once(const std::vector<HostGroups>& src, size_t i0, size
   else abi_check(mtblx_merge_emit(recs.data(), ns, mode, &out, ws.p, wsb, nullptr), "mtblx_merge_emit");
   hip_check(hipDeviceSynchronize(), "sync");
   const uint32_t flags = download<uint32_t>(fl.p, 1)[0];
-  if (flags & MTBLX_MERGE_BADVALUE) throw MergeError();
+  if (flags & MTBLX_MERGE_BADVALUE) throw MergeError(rd);
   if (flags) throw std::runtime_error("mtblx_merge_emit: flags set");
   HostGroups r;
   r.ke = download<uint64_t>(ke.p, tot[0]);
@@ -1536,7 +1570,7 @@ inline SegGroups merge_seg_once(const std::vector<HostGroups>& src, const SegOff
               "mtblx_merge_seg_emit");
   hip_check(hipDeviceSynchronize(), "sync");
   const uint32_t flags = download<uint32_t>(fl.p, 1)[0];
-  if (flags & MTBLX_MERGE_BADVALUE) throw MergeError();
+  if (flags & MTBLX_MERGE_BADVALUE) throw MergeError(rd);
   if (flags) throw std::runtime_error("mtblx_merge_seg_emit: flags set");
   SegGroups r;
   r.seg_end = download<uint64_t>(se.p, nseg);
@@ -1821,7 +1855,7 @@ inline HostGroups sort_once(const HostGroups& s, int mode, const mtblx_reduce* r
   else abi_check(mtblx_sort_emit(&rec, mode, &out, ws.p, wsb, nullptr), "mtblx_sort_emit");
   hip_check(hipDeviceSynchronize(), "sync");
   const uint32_t flags = download<uint32_t>(fl.p, 1)[0];
-  if (flags & MTBLX_MERGE_BADVALUE) throw MergeError();
+  if (flags & MTBLX_MERGE_BADVALUE) throw MergeError(rd);
   if (flags) throw std::runtime_error("mtblx_sort_emit: flags set");
   HostGroups r;
   r.ke = download<uint64_t>(ke.p, tot[0]);

@@ -734,13 +734,48 @@ int mtblx_sort_plan_timed(const mtblx_records* in, uint64_t* totals, void* works
  * the groups that cross a tile of 1024 merged records), hence not const.  MTBLX_MERGE_OVERFLOW and
  * MTBLX_MERGE_NOT_PLANNED as in the plain emits.  MTBLX_E_INVAL, before any device work: a NULL spec,
  * nfields 0 or above MTBLX_REDUCE_MAX_FIELDS, an op above MTBLX_REDUCE_MAX, and everything the plain
- * emits refuse. */
+ * emits refuse.
+ *
+ * Varint-coded values: MTBLX_REDUCE_VARINT OR-ed into every op[f] (all nfields of them or none: a mix
+ * is MTBLX_E_INVAL before any device work, as is an op whose other bits exceed MTBLX_REDUCE_MAX).  It
+ * is accepted by mtblx_merge_emit_reduce, mtblx_sort_emit_reduce, mtblx_merge_seg_emit_reduce,
+ * mtblx_scan_reduce and mtblx_reduce_segments.  This is the convention of the mtbl ecosystem: a value
+ * is a sequence of LEB128 varints, merged by decode -> min / max / sum -> re-encode.
+ *  - A value is well-formed iff it is exactly F = nfields varints back to back as varint_decode64
+ *    (src/varint.rs:78-97) reads them: for each field the decoder is applied to the rest of the value
+ *    and must consume at least one byte, and after the F-th field nothing is left.  The decoder's own
+ *    behaviour is kept: it looks at no more than 10 bytes per field; a field with no terminator
+ *    among them is an error (consumed 0); an empty rest is an error (the reference would panic);
+ *    non-canonical encodings (0x80 0x00) are accepted; bits above 2^64 in a tenth byte are dropped,
+ *    as the reference's shifts drop them.  Any other value is "bad".
+ *  - A group of one value comes out unchanged, whatever its bytes (not re-encoded, bad or not).
+ *  - A group of two or more well-formed values gives field f = op[f] over the decoded u64s (SUM mod
+ *    2^64, unsigned MIN / MAX), the F results encoded canonically by varint_encode64
+ *    (src/varint.rs:64-76) back to back.
+ *  - A group of two or more with a bad value sets MTBLX_MERGE_BADVALUE; its slot is as long as its
+ *    first value and holds that value, so the layout stays defined.
+ *  - In the aggregating calls fields[] stay u64 words, a bad value is counted in nbad and left out.
+ * The outputs are canonical and a group of one passes through, so applying the spec per round of
+ * sources, per Sorter chunk and again over the chunks gives the bytes of one application: decoding
+ * a canonical partial result gives back the number it encodes, the ops are associative and
+ * commutative, and the final encoding depends on the final numbers alone.  A bad value survives
+ * every round unchanged (alone in its group it passes through; with a partner it is the error).
+ * With VARINT the output layout is NOT MTBLX_MERGE_FIRST's: a result is as long as its result needs,
+ * longer than the group's first value (0x7f + 0x01 -> 0x80 0x01) or shorter (a sum that wraps).  vals
+ * must hold up to totals[3] bytes (all kept value bytes); the bytes used are val_end[groups - 1];
+ * keys, key_end and val_end as in MTBLX_MERGE_FIRST mode.  totals[3] is enough because a group's
+ * encoded result never exceeds the sum of its inputs' lengths, field by field: len(a + b) <=
+ * max(la, lb) + 1 <= la + lb (la, lb >= 1), min / max give <= max(la, lb), and a sum that wraps had
+ * a 10-byte operand; non-canonical inputs only widen the margin.  The workspace is the same (its
+ * size counts one more per-tile array); val_end is written, scanned in place and read by the call. */
 #define MTBLX_REDUCE_SUM 0
 #define MTBLX_REDUCE_MIN 1
 #define MTBLX_REDUCE_MAX 2
 #define MTBLX_REDUCE_MAX_FIELDS 8
+#define MTBLX_REDUCE_VARINT 0x10u   /* OR-ed into every op[f]: the fields are LEB128 varints back to back */
 #define MTBLX_MERGE_BADVALUE 4u     /* *flags of the two calls below: a group of two or more holds a
-                                       value that is not 8 * nfields bytes long                         */
+                                       value that is not 8 * nfields bytes long (VARINT: not nfields
+                                       varints back to back)                                            */
 typedef struct mtblx_reduce {
   uint32_t nfields;
   uint8_t op[MTBLX_REDUCE_MAX_FIELDS];
@@ -808,7 +843,9 @@ int mtblx_merge_seg_plan_timed(const mtblx_records* src, const uint64_t* const* 
 
 /* ---- Aggregating scans: a reduce spec folded over all the records a query matches ----
  * (csrc/scan.hip, csrc/reduce_seg.hip, DESIGN.md §4 "Aggregating scans").  The spec is the
- * mtblx_reduce of the device merge functions: F = nfields little-endian u64 fields, W = 8 * F.  For
+ * mtblx_reduce of the device merge functions: F = nfields little-endian u64 fields, W = 8 * F (with
+ * MTBLX_REDUCE_VARINT: F varints back to back; "not exactly W bytes long" below then reads "not
+ * well-formed", see "Varint-coded values" above; fields[] are u64 words either way).  For
  * one query (or one segment), over the records it yields:
  *    nrec       the records yielded (mtblx_scan_result.nrec; the segment's length);
  *    nbad       those among them whose value is not exactly W bytes long: left out of the reduction

@@ -163,12 +163,13 @@ extern "C" int mtblx_merge_impl_emit(const mtblx_records* src, uint32_t nsrc, in
   return hipGetLastError() == hipSuccess ? MTBLX_OK : MTBLX_E_HIP;
 }
 
-// a reduce spec as the merge function: k_merge_emit in FIRST mode (the layout), then the segmented
-// reduction over the groups of two or more (reduce_dev.h).  The workspace's edge array is written
+// a reduce spec as the merge function (reduce_dev.h, reduce_emit): u64le fields in MTBLX_MERGE_FIRST's
+// layout, or varint-coded fields in a layout of their own.  The workspace's per-tile arrays are written
 extern "C" int mtblx_merge_impl_emit_reduce(const mtblx_records* src, uint32_t nsrc, const mtblx_reduce* spec,
                                             const mtblx_merged* out, void* ws, hipStream_t s) {
   RSpec sp;
-  if (!reduce_spec(spec, &sp)) return MTBLX_E_INVAL;
+  bool varint;
+  if (!reduce_spec(spec, &sp, &varint)) return MTBLX_E_INVAL;
   SrcTab t;
   const uint64_t n64 = fill_tab(src, nsrc, &t);
   if (n64 == UINT64_MAX) return MTBLX_E_INVAL;
@@ -177,11 +178,6 @@ extern "C" int mtblx_merge_impl_emit_reduce(const mtblx_records* src, uint32_t n
   uint8_t* w = static_cast<uint8_t*>(ws);
   if (hipMemsetAsync(out->flags, 0, 4, s) != hipSuccess) return MTBLX_E_HIP;
   const Handle* hf = reinterpret_cast<const Handle*>(w + (passes_for(nsrc) & 1 ? L.h1 : L.h0));
-  MTBLX_LAUNCH((MTBLX_R(w, L.total), MTBLX_R(out->keys, out->keys_cap), MTBLX_R(out->key_end, out->key_end_cap),
-                MTBLX_R(out->vals, out->vals_cap), MTBLX_R(out->val_end, out->val_end_cap), MTBLX_R(out->flags, 4)),
-               k_merge_emit, dim3(n ? (unsigned)(((uint64_t)n + kEmitTile - 1) / kEmitTile) : 1u), dim3(kThreads), 0, s, t,
-               reinterpret_cast<const uint64_t*>(w + L.hdr), hf, w + L.flag, group_out(w, L), *out, MTBLX_MERGE_FIRST, n,
-               planned_mark(n, nsrc));
-  if (n) reduce_launch(t, w, L, hf, *out, sp, spec->nfields, n, planned_mark(n, nsrc), s);
+  reduce_emit(t, w, L.total, L, hf, *out, sp, varint, spec->nfields, n, planned_mark(n, nsrc), s);
   return hipGetLastError() == hipSuccess ? MTBLX_OK : MTBLX_E_HIP;
 }

@@ -51,6 +51,10 @@ enum { H_GROUPS = 0, H_KEYB, H_NVAL, H_VALB, H_DROPPED, H_FLAGS, H_SKIP, H_PLANN
        H_SEGSKIP,   // merge_seg.hip: u64 words from the header to the per-segment skip array
        H_WORDS = 32 };
 constexpr int kReduceEdgeWords = 18;   // u64 words per tile of the device merge functions' edge array (reduce_dev.h)
+// k_merge_emit's internal mode, after the public MTBLX_MERGE_* ones: the last step of the varint reduce
+// emit (reduce_dev.h): keys and key_end as ever, and only the groups of one bring their value, to
+// where the scanned val_end says their slot begins; val_end itself is not written
+constexpr int kEmitSingles = 16;
 constexpr int kChan = 6;   // groups, key bytes, values, value bytes, first-value bytes, last-value bytes
 
 struct alignas(16) Handle {
@@ -501,6 +505,21 @@ __global__ void __launch_bounds__(kThreads) k_merge_emit(SrcTab t, const uint64_
     } else if (mode == MTBLX_MERGE_LAST) {
       copy = end = tail;
       off = g.loff[i];
+    } else if (mode == kEmitSingles) {
+      copy = head && tail;
+      end = false;
+      if (copy) {
+        if (8 * (gi + 1) <= o.val_end_cap) {
+          off = 0;
+          if (gi) {
+            MTBLX_CHK(o.val_end + gi - 1, 8);
+            off = o.val_end[gi - 1];
+          }
+        } else {
+          copy = false;
+          over = true;
+        }
+      }
     }
     if (copy) {
       if (off + vlen <= o.vals_cap) copy16(o.vals + off, vp, vlen, l); else over = true;
@@ -519,7 +538,7 @@ __global__ void __launch_bounds__(kThreads) k_merge_emit(SrcTab t, const uint64_
 
 // ---- host side ----
 struct Layout {
-  size_t hdr, h0, h1, flag, gi, vi, koff, voff, foff, loff, tiles, edges, total;
+  size_t hdr, h0, h1, flag, gi, vi, koff, voff, foff, loff, tiles, edges, vtiles, total;
   uint32_t ntiles;
 };
 
@@ -541,6 +560,7 @@ Layout layout(uint64_t n) {
   L.loff = p; p += up256(8 * n);
   L.tiles = p; p += up256(8ull * kChan * L.ntiles);
   L.edges = p; p += up256(8ull * kReduceEdgeWords * L.ntiles);   // the reducers' per-tile edge records (reduce_dev.h)
+  L.vtiles = p; p += up256(8ull * L.ntiles);   // the varint reduce emit's per-tile sums of val_end (reduce_dev.h)
   L.total = p;
   return L;
 }

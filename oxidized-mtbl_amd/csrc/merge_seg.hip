@@ -330,13 +330,13 @@ extern "C" int mtblx_merge_seg_impl_plan(const mtblx_records* src, const uint64_
   return MTBLX_OK;
 }
 
-// spec == NULL: the plain emit in `mode`; else the reduce emit (k_merge_emit in FIRST mode, then the
-// segmented reduction of reduce_dev.h).  The handles were stripped by the plan: both read them as
-// the Merger's.
+// spec == NULL: the plain emit in `mode`; else the reduce emit (reduce_emit of reduce_dev.h).  The
+// handles were stripped by the plan: both read them as the Merger's.
 extern "C" int mtblx_merge_seg_impl_emit(const mtblx_records* src, uint32_t nsrc, uint32_t nseg, int mode,
                                          const mtblx_reduce* spec, const mtblx_merged* out, void* ws, hipStream_t s) {
   RSpec sp{};
-  if (spec && !reduce_spec(spec, &sp)) return MTBLX_E_INVAL;
+  bool varint = false;
+  if (spec && !reduce_spec(spec, &sp, &varint)) return MTBLX_E_INVAL;
   SrcTab t;
   const uint64_t n64 = fill_tab(src, nsrc, &t);
   if (n64 == UINT64_MAX) return MTBLX_E_INVAL;
@@ -347,12 +347,15 @@ extern "C" int mtblx_merge_seg_impl_emit(const mtblx_records* src, uint32_t nsrc
   if (hipMemsetAsync(out->flags, 0, 4, s) != hipSuccess) return MTBLX_E_HIP;
   const Handle* hf = reinterpret_cast<const Handle*>(w + (passes_for(nsrc) & 1 ? L.h1 : L.h0));
   const uint64_t mark = planned_mark(n, nsrc, nseg);
+  if (spec) {
+    reduce_emit(t, w, S.total, L, hf, *out, sp, varint, spec->nfields, n, mark, s);
+    return hipGetLastError() == hipSuccess ? MTBLX_OK : MTBLX_E_HIP;
+  }
   MTBLX_LAUNCH((MTBLX_R(w, S.total), MTBLX_R(out->keys, out->keys_cap), MTBLX_R(out->key_end, out->key_end_cap),
                 MTBLX_R(out->vals, out->vals_cap), MTBLX_R(out->val_end, out->val_end_cap),
                 MTBLX_R(out->grp_end, out->grp_end_cap), MTBLX_R(out->flags, 4)),
                k_merge_emit, dim3(n ? (unsigned)(((uint64_t)n + kEmitTile - 1) / kEmitTile) : 1u), dim3(kThreads), 0, s, t,
                reinterpret_cast<const uint64_t*>(w + L.hdr), hf, w + L.flag, group_out(w, L), *out,
-               spec ? MTBLX_MERGE_FIRST : mode, n, mark);
-  if (spec && n) reduce_launch(t, w, L, hf, *out, sp, spec->nfields, n, mark, s);
+               mode, n, mark);
   return hipGetLastError() == hipSuccess ? MTBLX_OK : MTBLX_E_HIP;
 }

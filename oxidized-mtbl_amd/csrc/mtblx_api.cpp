@@ -205,10 +205,19 @@ extern "C" int mtblx_merge_impl_emit_reduce(const mtblx_records* src, uint32_t n
 extern "C" int mtblx_sort_impl_emit_reduce(const mtblx_records* in, const mtblx_reduce* spec, const mtblx_merged* out,
                                            void* ws, hipStream_t s);
 
-static int reduce_check(const mtblx_reduce* spec, const mtblx_merged* out) {
+// a reduce spec: 1 to 8 ops, each SUM / MIN / MAX, with MTBLX_REDUCE_VARINT on all of them or on none
+static int spec_check(const mtblx_reduce* spec) {
   if (!spec || spec->nfields < 1 || spec->nfields > MTBLX_REDUCE_MAX_FIELDS) return MTBLX_E_INVAL;
-  for (uint32_t f = 0; f < spec->nfields; ++f)
-    if (spec->op[f] > MTBLX_REDUCE_MAX) return MTBLX_E_INVAL;
+  uint32_t nv = 0;
+  for (uint32_t f = 0; f < spec->nfields; ++f) {
+    if ((spec->op[f] & ~MTBLX_REDUCE_VARINT) > MTBLX_REDUCE_MAX) return MTBLX_E_INVAL;
+    if (spec->op[f] & MTBLX_REDUCE_VARINT) ++nv;
+  }
+  return nv == 0 || nv == spec->nfields ? MTBLX_OK : MTBLX_E_INVAL;
+}
+
+static int reduce_check(const mtblx_reduce* spec, const mtblx_merged* out) {
+  if (spec_check(spec) != MTBLX_OK) return MTBLX_E_INVAL;
   if (!out || !out->flags) return MTBLX_E_INVAL;
   if ((!out->keys && out->keys_cap) || (!out->key_end && out->key_end_cap) || (!out->vals && out->vals_cap) ||
       (!out->val_end && out->val_end_cap))
@@ -396,13 +405,6 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
 extern "C" int mtblx_reduce_seg_impl(const mtblx_records* recs, const uint64_t* seg_lo, const uint64_t* seg_hi,
                                      uint32_t nseg, const mtblx_reduce* spec, uint64_t* fields, uint64_t* nbad,
                                      uint32_t* flags, hipStream_t s);
-
-static int spec_check(const mtblx_reduce* spec) {
-  if (!spec || spec->nfields < 1 || spec->nfields > MTBLX_REDUCE_MAX_FIELDS) return MTBLX_E_INVAL;
-  for (uint32_t f = 0; f < spec->nfields; ++f)
-    if (spec->op[f] > MTBLX_REDUCE_MAX) return MTBLX_E_INVAL;
-  return MTBLX_OK;
-}
 
 extern "C" int mtblx_scan_reduce(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
                                  uint64_t index_off, uint64_t index_len, const uint64_t* tab_start,

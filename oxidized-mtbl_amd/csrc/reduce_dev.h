@@ -26,6 +26,21 @@
 // No workgroup waits for another: the launches are ordered by the stream.  The ops are
 // associative and commutative and the results exact, so no result depends on evaluation order; the
 // output slots are unaligned and written with plain (packed) stores, never with atomics.
+//
+// Varint-coded values (ENC = R_VARINT; include/mtblx.h "Varint-coded values"): a value is F LEB128
+// varints back to back and a group's result is as long as its result needs, so the output has a
+// layout of its own and the emit (reduce_emit below) is
+//   length pass   k_reduce_tile / k_reduce_edges with LEN: the same reduction, and where the u64le
+//                 kernels store a result these write the group's encoded length to val_end[group];
+//                 a group of one writes its own value's length, a group with a bad value its first
+//                 value's (the layout stays defined; MTBLX_MERGE_BADVALUE is set)
+//   k_vend_*      the in-place inclusive scan of val_end[0, groups): tile sums, one workgroup over
+//                 the tile sums, apply (three launches, a per-tile array in the workspace)
+//   store pass    the reduction again; a good group's result is encoded at val_end[group - 1], a
+//                 bad group's first value copied there by the one thread that holds the group
+//   k_merge_emit  in kEmitSingles mode: keys, key_end, and every group of one copied to its slot
+// Every store is checked against the capacities and sets MTBLX_MERGE_OVERFLOW as r_store does;
+// val_end entries past val_end_cap are neither written nor scanned nor read.
 #pragma once
 #include "merge_dev.h"
 #include "reduce_ops.h"   // RSpec, the op table, Seg and its join: shared with reduce_seg.hip and scan.hip
@@ -47,11 +62,53 @@ __device__ __forceinline__ bool r_store(const mtblx_merged& o, uint64_t off, con
   return true;
 }
 
-template <int F>
+// A varint group of two or more is finished by the one thread that holds its result: g the group,
+// hidx its head's record, v the reduced fields, bad: it holds a value that is not F varints.  LEN:
+// val_end[g] = the result's encoded length (bad: the first value's).  Else, after the scan of
+// val_end: the result encoded (bad: the first value copied) at val_end[g - 1].  -> false on overflow
+template <int F, bool LEN>
+__device__ __forceinline__ bool r_finish_varint(const SrcTab& t, const Handle* h, const mtblx_merged& o, uint64_t g,
+                                                uint32_t hidx, bool bad, const uint64_t* v) {
+  const uint8_t* fp = nullptr;
+  uint64_t len;
+  if (bad) {
+    MTBLX_CHK(h + hidx, 16);
+    const Handle c = h[hidx];
+    uint64_t vs;
+    len = val_len(t, c.src, c.idx, &vs);
+    fp = t.s[c.src].vals + vs;
+  } else {
+    len = r_varint_len_all<F>(v);
+  }
+  if (8 * (g + 1) > o.val_end_cap) return false;
+  if (LEN) {
+    MTBLX_CHK(o.val_end + g, 8);
+    o.val_end[g] = len;
+    return true;
+  }
+  uint64_t off = 0;
+  if (g) {
+    MTBLX_CHK(o.val_end + g - 1, 8);
+    off = o.val_end[g - 1];
+  }
+  if (off + len > o.vals_cap) return false;
+  if (len) MTBLX_CHK(o.vals + off, len);
+  if (bad) {
+    for (uint64_t j = 0; j < len; ++j) o.vals[off + j] = fp[j];
+  } else {
+    r_store_varint<F>(o.vals + off, v);
+  }
+  return true;
+}
+
+// ENC = R_U64LE: as described at the head of this file (LEN is false, gidx unused).  ENC = R_VARINT:
+// the length pass (LEN) or the store pass of the varint emit; gidx = the group of every record
+template <int F, int ENC, bool LEN>
 __global__ void __launch_bounds__(kThreads) k_reduce_tile(SrcTab t, const uint64_t* hdr, const Handle* h,
-                                                          const uint8_t* flag, const uint64_t* foff, mtblx_merged o,
-                                                          uint64_t* edges, RSpec sp, uint32_t n, uint64_t planned) {
-  if (hdr[H_PLANNED] != planned) return;   // k_merge_emit has reported it
+                                                          const uint8_t* flag, const uint64_t* foff,
+                                                          const uint32_t* gidx, mtblx_merged o, uint64_t* edges,
+                                                          RSpec sp, uint32_t n, uint64_t planned) {
+  if (hdr[H_PLANNED] != planned) return;   // k_merge_emit reports it
   __shared__ uint64_t wv[kThreads / 64][F];   // the waves' runs
   __shared__ uint32_t wfl[kThreads / 64], whi[kThreads / 64];
   constexpr uint64_t W = 8u * F;
@@ -61,7 +118,7 @@ __global__ void __launch_bounds__(kThreads) k_reduce_tile(SrcTab t, const uint64
   // st: bit 0 head, bit 1 tail, bit 2 kept (in range and not dropped), bit 3 bad
   uint64_t v[kPer][F];
   uint32_t st[kPer];
-  bool anybad = false;
+  bool anybad = false, over = false;
 #pragma unroll
   for (int k = 0; k < kPer; ++k) {
     const uint64_t i = i0 + k;
@@ -74,16 +131,35 @@ __global__ void __launch_bounds__(kThreads) k_reduce_tile(SrcTab t, const uint64
     if (fl & 2) continue;
     const bool head = fl & 1, tail = i + 1 == n || (flag[i + 1] & 1);
     st[k] = (head ? 1u : 0u) | (tail ? 2u : 0u) | 4u;
-    if (head && tail) continue;   // a group of one: finished by k_merge_emit, whatever its length
+    // a group of one: finished by k_merge_emit, whatever its bytes (the varint length pass gives it its length)
+    if (head && tail && !(ENC == R_VARINT && LEN)) continue;
     MTBLX_CHK(h + i, 16);
     const Handle c = h[i];
     uint64_t vs;
     const uint64_t vlen = val_len(t, c.src, c.idx, &vs);
-    if (vlen == W) {
-      const uint8_t* vp = t.s[c.src].vals + vs;   // any alignment
-#pragma unroll
-      for (int f = 0; f < F; ++f) v[k][f] = *reinterpret_cast<const u64u*>(vp + 8 * f);
+    if (head && tail) {
+      MTBLX_CHK(gidx + i, 4);
+      const uint64_t g = gidx[i];
+      if (8 * (g + 1) <= o.val_end_cap) {
+        MTBLX_CHK(o.val_end + g, 8);
+        o.val_end[g] = vlen;
+      } else {
+        over = true;
+      }
+      continue;
+    }
+    const uint8_t* vp = t.s[c.src].vals + vs;   // any alignment
+    bool good;
+    if (ENC == R_VARINT) {
+      good = r_load_varint<F, false>(vp, vlen, v[k]);
     } else {
+      good = vlen == W;
+      if (good) {
+#pragma unroll
+        for (int f = 0; f < F; ++f) v[k][f] = *reinterpret_cast<const u64u*>(vp + 8 * f);
+      }
+    }
+    if (!good) {
       st[k] |= 8u;
       anybad = true;
     }
@@ -129,7 +205,6 @@ __global__ void __launch_bounds__(kThreads) k_reduce_tile(SrcTab t, const uint64
     }
   acc = seg_join<F>(sp, before, acc);   // everything of the tile before this thread's records
   uint64_t* edge = edges + (uint64_t)blockIdx.x * kEdgeWords;
-  bool over = false;
 #pragma unroll
   for (int k = 0; k < kPer; ++k) {
     if (!(st[k] & 4u)) continue;
@@ -147,7 +222,12 @@ __global__ void __launch_bounds__(kThreads) k_reduce_tile(SrcTab t, const uint64
     e.fl = (st[k] & 1u) | ((st[k] & 8u) >> 2);
     e.hidx = (uint32_t)i;
     acc = seg_join<F>(sp, acc, e);
-    if ((st[k] & 3u) == 2u && acc.fl == 1u) {   // the tail of a group of two or more, all of it here and good
+    if (ENC == R_VARINT) {
+      if ((st[k] & 3u) == 2u && (acc.fl & 1u)) {   // the tail of a group of two or more, all of it here
+        MTBLX_CHK(gidx + i, 4);
+        if (!r_finish_varint<F, LEN>(t, h, o, gidx[i], acc.hidx, acc.fl & 2u, acc.v)) over = true;
+      }
+    } else if ((st[k] & 3u) == 2u && acc.fl == 1u) {   // the tail of a group of two or more, all of it here and good
       MTBLX_CHK(foff + i, 8);
       if (!r_store<F>(o, foff[i] - W, acc.v)) over = true;
     }
@@ -176,8 +256,9 @@ __global__ void __launch_bounds__(kThreads) k_reduce_tile(SrcTab t, const uint64
   }
 }
 
-template <int F>
-__global__ void __launch_bounds__(kThreads) k_reduce_edges(const uint64_t* hdr, const uint64_t* foff, mtblx_merged o,
+template <int F, int ENC, bool LEN>
+__global__ void __launch_bounds__(kThreads) k_reduce_edges(SrcTab t, const uint64_t* hdr, const Handle* h,
+                                                           const uint64_t* foff, const uint32_t* gidx, mtblx_merged o,
                                                            const uint64_t* edges, RSpec sp, uint32_t ntiles,
                                                            uint64_t planned) {
   if (hdr[H_PLANNED] != planned) return;
@@ -215,41 +296,157 @@ __global__ void __launch_bounds__(kThreads) k_reduce_edges(const uint64_t* hdr, 
     for (int f = 0; f < F; ++f)
       p[f] = r_apply(r_op(sp, f), p[f], (uint64_t)__shfl_xor((unsigned long long)p[f], s, 64));
   }
-  if (__ballot(bad)) return;   // the records themselves have set MTBLX_MERGE_BADVALUE
+  const bool anybad = __ballot(bad) != 0;   // the records themselves have set MTBLX_MERGE_BADVALUE
+  const uint32_t hidx = (uint32_t)(meta >> 32);
+  if (ENC == R_VARINT) {
+    if (lane == 0) {
+      MTBLX_CHK(gidx + hidx, 4);
+      if (!r_finish_varint<F, LEN>(t, h, o, gidx[hidx], hidx, anybad, p)) atomicOr(o.flags, MTBLX_MERGE_OVERFLOW);
+    }
+    return;
+  }
+  if (anybad) return;
   if (lane == 0) {
-    const uint32_t hidx = (uint32_t)(meta >> 32);
     MTBLX_CHK(foff + hidx, 8);
     if (!r_store<F>(o, foff[hidx], p)) atomicOr(o.flags, MTBLX_MERGE_OVERFLOW);
   }
 }
 
-// ---- host side ----
-template <int F>
-void reduce_launch_f(const SrcTab& t, uint8_t* w, const Layout& L, const Handle* hf, const mtblx_merged& o, RSpec sp,
-                     uint32_t n, uint64_t planned, hipStream_t s) {
-  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(w + L.hdr);
-  const uint64_t* foff = reinterpret_cast<const uint64_t*>(w + L.foff);
-  uint64_t* edges = reinterpret_cast<uint64_t*>(w + L.edges);
-  MTBLX_LAUNCH((MTBLX_R(w, L.total), MTBLX_R(o.vals, o.vals_cap), MTBLX_R(o.flags, 4)), k_reduce_tile<F>,
-               dim3(L.ntiles), dim3(kThreads), 0, s, t, hdr, hf, w + L.flag, foff, o, edges, sp, n, planned);
-  MTBLX_LAUNCH((MTBLX_R(w, L.total), MTBLX_R(o.vals, o.vals_cap), MTBLX_R(o.flags, 4)), k_reduce_edges<F>,
-               dim3((L.ntiles + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, s, hdr, foff, o, edges, sp,
-               L.ntiles, planned);
+// ---- the varint emit's scan: val_end[0, m) -> its inclusive prefix sums, in place; m = the groups
+// val_end can hold.  A workgroup owns kTile entries, kPer per thread; vt = one sum per tile ----
+__device__ __forceinline__ uint64_t vend_count(const uint64_t* hdr, const mtblx_merged& o) {
+  const uint64_t g = hdr[H_GROUPS], c = o.val_end_cap / 8;
+  return g < c ? g : c;
 }
 
-// after k_merge_emit in FIRST mode on the same stream; n != 0
-void reduce_launch(const SrcTab& t, uint8_t* w, const Layout& L, const Handle* hf, const mtblx_merged& o, RSpec sp,
-                   uint32_t nfields, uint32_t n, uint64_t planned, hipStream_t s) {
-  switch (nfields) {
-    case 1: reduce_launch_f<1>(t, w, L, hf, o, sp, n, planned, s); break;
-    case 2: reduce_launch_f<2>(t, w, L, hf, o, sp, n, planned, s); break;
-    case 3: reduce_launch_f<3>(t, w, L, hf, o, sp, n, planned, s); break;
-    case 4: reduce_launch_f<4>(t, w, L, hf, o, sp, n, planned, s); break;
-    case 5: reduce_launch_f<5>(t, w, L, hf, o, sp, n, planned, s); break;
-    case 6: reduce_launch_f<6>(t, w, L, hf, o, sp, n, planned, s); break;
-    case 7: reduce_launch_f<7>(t, w, L, hf, o, sp, n, planned, s); break;
-    default: reduce_launch_f<8>(t, w, L, hf, o, sp, n, planned, s); break;
+__global__ void __launch_bounds__(kThreads) k_vend_sums(const uint64_t* hdr, mtblx_merged o, uint64_t* vt,
+                                                        uint64_t planned) {
+  if (hdr[H_PLANNED] != planned) return;
+  __shared__ uint64_t wsum[kThreads / 64];
+  const uint64_t m = vend_count(hdr, o);
+  const uint64_t i0 = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * kPer;
+  uint64_t sum = 0;
+#pragma unroll
+  for (int k = 0; k < kPer; ++k)
+    if (i0 + k < m) {
+      MTBLX_CHK(o.val_end + i0 + k, 8);
+      sum += o.val_end[i0 + k];
+    }
+  uint64_t tot;
+  (void)block_scan(sum, wsum, &tot);
+  if (threadIdx.x == 0) {
+    MTBLX_CHK(vt + blockIdx.x, 8);
+    vt[blockIdx.x] = tot;
   }
 }
+
+// one workgroup: the tile sums -> their exclusive prefixes, in place
+__global__ void __launch_bounds__(kThreads) k_vend_scan(const uint64_t* hdr, uint64_t* vt, uint32_t ntiles,
+                                                        uint64_t planned) {
+  if (hdr[H_PLANNED] != planned) return;
+  __shared__ uint64_t wsum[kThreads / 64];
+  uint64_t carry = 0;
+  for (uint32_t b = 0; b < ntiles; b += kThreads) {
+    const uint32_t i = b + threadIdx.x;
+    if (i < ntiles) MTBLX_CHK(vt + i, 8);
+    const uint64_t v = i < ntiles ? vt[i] : 0;
+    uint64_t tot;
+    const uint64_t e = block_scan(v, wsum, &tot);
+    if (i < ntiles) vt[i] = carry + e;
+    carry += tot;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) k_vend_apply(const uint64_t* hdr, mtblx_merged o, const uint64_t* vt,
+                                                         uint64_t planned) {
+  if (hdr[H_PLANNED] != planned) return;
+  __shared__ uint64_t wsum[kThreads / 64];
+  const uint64_t m = vend_count(hdr, o);
+  const uint64_t i0 = (uint64_t)blockIdx.x * kTile + (uint64_t)threadIdx.x * kPer;
+  uint64_t x[kPer], sum = 0;
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    x[k] = 0;
+    if (i0 + k < m) {
+      MTBLX_CHK(o.val_end + i0 + k, 8);
+      x[k] = o.val_end[i0 + k];
+    }
+    sum += x[k];
+  }
+  uint64_t tot;
+  MTBLX_CHK(vt + blockIdx.x, 8);
+  uint64_t e = block_scan(sum, wsum, &tot) + vt[blockIdx.x];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    e += x[k];
+    if (i0 + k < m) o.val_end[i0 + k] = e;
+  }
+}
+
+// ---- host side ----
+#define MTBLX_REDUCE_RANGES \
+  (MTBLX_R(w, wtotal), MTBLX_R(o.vals, o.vals_cap), MTBLX_R(o.val_end, o.val_end_cap), MTBLX_R(o.flags, 4))
+
+template <int F, int ENC, bool LEN>
+void reduce_pass(const SrcTab& t, uint8_t* w, size_t wtotal, const Layout& L, const Handle* hf, const mtblx_merged& o,
+                 RSpec sp, uint32_t n, uint64_t planned, hipStream_t s) {
+  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(w + L.hdr);
+  const uint64_t* foff = reinterpret_cast<const uint64_t*>(w + L.foff);
+  const uint32_t* gidx = reinterpret_cast<const uint32_t*>(w + L.gi);
+  uint64_t* edges = reinterpret_cast<uint64_t*>(w + L.edges);
+  MTBLX_LAUNCH(MTBLX_REDUCE_RANGES, (k_reduce_tile<F, ENC, LEN>), dim3(L.ntiles), dim3(kThreads), 0, s, t, hdr, hf,
+               w + L.flag, foff, gidx, o, edges, sp, n, planned);
+  MTBLX_LAUNCH(MTBLX_REDUCE_RANGES, (k_reduce_edges<F, ENC, LEN>),
+               dim3((L.ntiles + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, s, t, hdr, hf, foff, gidx, o,
+               edges, sp, L.ntiles, planned);
+}
+
+template <int F>
+void reduce_launch_f(const SrcTab& t, uint8_t* w, size_t wtotal, const Layout& L, const Handle* hf,
+                     const mtblx_merged& o, RSpec sp, bool varint, uint32_t n, uint64_t planned, hipStream_t s) {
+  if (!varint) {
+    reduce_pass<F, R_U64LE, false>(t, w, wtotal, L, hf, o, sp, n, planned, s);
+    return;
+  }
+  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(w + L.hdr);
+  uint64_t* vt = reinterpret_cast<uint64_t*>(w + L.vtiles);
+  reduce_pass<F, R_VARINT, true>(t, w, wtotal, L, hf, o, sp, n, planned, s);
+  MTBLX_LAUNCH(MTBLX_REDUCE_RANGES, k_vend_sums, dim3(L.ntiles), dim3(kThreads), 0, s, hdr, o, vt, planned);
+  MTBLX_LAUNCH(MTBLX_REDUCE_RANGES, k_vend_scan, dim3(1), dim3(kThreads), 0, s, hdr, vt, L.ntiles, planned);
+  MTBLX_LAUNCH(MTBLX_REDUCE_RANGES, k_vend_apply, dim3(L.ntiles), dim3(kThreads), 0, s, hdr, o, vt, planned);
+  reduce_pass<F, R_VARINT, false>(t, w, wtotal, L, hf, o, sp, n, planned, s);
+}
+
+// The reduce emit of the Merger, the Sorter and the segmented merge, on stream s.  u64le: k_merge_emit
+// in FIRST mode, then the reduction over the groups of two or more.  varint: the passes at the head
+// of this file, k_merge_emit (kEmitSingles) last.  wtotal: the workspace's bytes (bounds build)
+void reduce_emit(const SrcTab& t, uint8_t* w, size_t wtotal, const Layout& L, const Handle* hf, const mtblx_merged& o,
+                 RSpec sp, bool varint, uint32_t nfields, uint32_t n, uint64_t planned, hipStream_t s) {
+  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(w + L.hdr);
+  const dim3 eg(n ? (unsigned)(((uint64_t)n + kEmitTile - 1) / kEmitTile) : 1u);
+  if (!varint)
+    MTBLX_LAUNCH((MTBLX_R(w, wtotal), MTBLX_R(o.keys, o.keys_cap), MTBLX_R(o.key_end, o.key_end_cap),
+                  MTBLX_R(o.vals, o.vals_cap), MTBLX_R(o.val_end, o.val_end_cap), MTBLX_R(o.flags, 4)),
+                 k_merge_emit, eg, dim3(kThreads), 0, s, t, hdr, hf, w + L.flag, group_out(w, L), o, MTBLX_MERGE_FIRST,
+                 n, planned);
+  if (n) {
+    switch (nfields) {
+      case 1: reduce_launch_f<1>(t, w, wtotal, L, hf, o, sp, varint, n, planned, s); break;
+      case 2: reduce_launch_f<2>(t, w, wtotal, L, hf, o, sp, varint, n, planned, s); break;
+      case 3: reduce_launch_f<3>(t, w, wtotal, L, hf, o, sp, varint, n, planned, s); break;
+      case 4: reduce_launch_f<4>(t, w, wtotal, L, hf, o, sp, varint, n, planned, s); break;
+      case 5: reduce_launch_f<5>(t, w, wtotal, L, hf, o, sp, varint, n, planned, s); break;
+      case 6: reduce_launch_f<6>(t, w, wtotal, L, hf, o, sp, varint, n, planned, s); break;
+      case 7: reduce_launch_f<7>(t, w, wtotal, L, hf, o, sp, varint, n, planned, s); break;
+      default: reduce_launch_f<8>(t, w, wtotal, L, hf, o, sp, varint, n, planned, s); break;
+    }
+  }
+  if (varint)
+    MTBLX_LAUNCH((MTBLX_R(w, wtotal), MTBLX_R(o.keys, o.keys_cap), MTBLX_R(o.key_end, o.key_end_cap),
+                  MTBLX_R(o.vals, o.vals_cap), MTBLX_R(o.val_end, o.val_end_cap), MTBLX_R(o.flags, 4)),
+                 k_merge_emit, eg, dim3(kThreads), 0, s, t, hdr, hf, w + L.flag, group_out(w, L), o, kEmitSingles, n,
+                 planned);
+}
+#undef MTBLX_REDUCE_RANGES
 
 }  // namespace

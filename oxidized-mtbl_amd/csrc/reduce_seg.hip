@@ -3,7 +3,8 @@
 //
 // Segment s is the records [seg_lo[s], seg_hi[s]) of one mtblx_records; per segment the F fields of
 // a reduce spec are reduced over the values that are exactly W = 8 * F bytes long, and the others are
-// counted in nbad[s].  Records in no segment bring nothing.
+// counted in nbad[s].  With a varint spec (ENC = R_VARINT) the values that count are those that are
+// exactly F varints back to back (reduce_ops.h, r_load_varint).  Records in no segment bring nothing.
 //   k_rseg_check  a thread per segment: seg_lo[s] <= seg_hi[s] <= seg_lo[s + 1], seg_hi[nseg - 1] <= n;
 //                 a violation sets MTBLX_REDUCE_BADSEG in *flags and the two kernels below return
 //                 without writing
@@ -115,7 +116,7 @@ __device__ __forceinline__ SegB<F> segb_shfl_up(const SegB<F>& x, int o) {
   return r;
 }
 
-template <int F>
+template <int F, int ENC>
 __global__ void __launch_bounds__(kSegThreads) k_rseg_tile(mtblx_records rec, const uint64_t* seg_lo,
                                                            const uint64_t* seg_hi, uint32_t nseg, RSpec sp,
                                                            uint64_t* fields, uint64_t* nbad, const uint32_t* flags) {
@@ -161,8 +162,11 @@ __global__ void __launch_bounds__(kSegThreads) k_rseg_tile(mtblx_records rec, co
       MTBLX_CHK(rec.val_end + i - 1, 8);
       vs = rec.val_end[i - 1];
     }
-    if (rec.val_end[i] - vs == W) {
-      const uint8_t* vp = rec.vals + vs;   // any alignment
+    const uint64_t vlen = rec.val_end[i] - vs;
+    const uint8_t* vp = rec.vals + vs;   // any alignment
+    if (ENC == R_VARINT) {
+      bad[k] = !r_load_varint<F, true>(vp, vlen, v[k]);
+    } else if (vlen == W) {
       MTBLX_CHK(vp, W);
 #pragma unroll
       for (int f = 0; f < F; ++f) v[k][f] = *reinterpret_cast<const ru64u*>(vp + 8 * f);
@@ -252,14 +256,21 @@ __global__ void __launch_bounds__(kSegThreads) k_rseg_tile(mtblx_records rec, co
   }
 }
 
-template <int F>
-void rseg_launch(const mtblx_records& rec, const uint64_t* seg_lo, const uint64_t* seg_hi, uint32_t nseg, RSpec sp,
-                 uint64_t* fields, uint64_t* nbad, uint32_t* flags, hipStream_t s) {
+template <int F, int ENC>
+void rseg_launch_e(const mtblx_records& rec, const uint64_t* seg_lo, const uint64_t* seg_hi, uint32_t nseg, RSpec sp,
+                   uint64_t* fields, uint64_t* nbad, uint32_t* flags, hipStream_t s) {
   const uint64_t ntiles = (rec.n + kSegTile - 1) / kSegTile;
   MTBLX_LAUNCH((MTBLX_R(rec.val_end, 8 * rec.n), rec.vals, MTBLX_R(seg_lo, 8ull * nseg), MTBLX_R(seg_hi, 8ull * nseg),
                 MTBLX_R(fields, 8ull * nseg * F), MTBLX_R(nbad, 8ull * nseg), MTBLX_R(flags, 4)),
-               k_rseg_tile<F>, dim3((unsigned)ntiles), dim3(kSegThreads), 0, s, rec, seg_lo, seg_hi, nseg, sp, fields,
-               nbad, flags);
+               (k_rseg_tile<F, ENC>), dim3((unsigned)ntiles), dim3(kSegThreads), 0, s, rec, seg_lo, seg_hi, nseg, sp,
+               fields, nbad, flags);
+}
+
+template <int F>
+void rseg_launch(bool varint, const mtblx_records& rec, const uint64_t* seg_lo, const uint64_t* seg_hi, uint32_t nseg,
+                 RSpec sp, uint64_t* fields, uint64_t* nbad, uint32_t* flags, hipStream_t s) {
+  if (varint) rseg_launch_e<F, R_VARINT>(rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s);
+  else rseg_launch_e<F, R_U64LE>(rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s);
 }
 
 }  // namespace
@@ -271,7 +282,8 @@ extern "C" int mtblx_reduce_seg_impl(const mtblx_records* recs, const uint64_t* 
                                      uint32_t nseg, const mtblx_reduce* spec, uint64_t* fields, uint64_t* nbad,
                                      uint32_t* flags, hipStream_t s) {
   RSpec sp;
-  if (!reduce_spec(spec, &sp)) return MTBLX_E_INVAL;
+  bool varint;
+  if (!reduce_spec(spec, &sp, &varint)) return MTBLX_E_INVAL;
   const uint32_t nf = spec->nfields;
   const mtblx_records rec = *recs;
   if (hipMemsetAsync(flags, 0, 4, s) != hipSuccess) return MTBLX_E_HIP;
@@ -285,14 +297,14 @@ extern "C" int mtblx_reduce_seg_impl(const mtblx_records* recs, const uint64_t* 
                nf, sp, flags);
   if (rec.n) {
     switch (nf) {
-      case 1: rseg_launch<1>(rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
-      case 2: rseg_launch<2>(rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
-      case 3: rseg_launch<3>(rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
-      case 4: rseg_launch<4>(rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
-      case 5: rseg_launch<5>(rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
-      case 6: rseg_launch<6>(rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
-      case 7: rseg_launch<7>(rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
-      default: rseg_launch<8>(rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
+      case 1: rseg_launch<1>(varint, rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
+      case 2: rseg_launch<2>(varint, rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
+      case 3: rseg_launch<3>(varint, rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
+      case 4: rseg_launch<4>(varint, rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
+      case 5: rseg_launch<5>(varint, rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
+      case 6: rseg_launch<6>(varint, rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
+      case 7: rseg_launch<7>(varint, rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
+      default: rseg_launch<8>(varint, rec, seg_lo, seg_hi, nseg, sp, fields, nbad, flags, s); break;
     }
   }
   return hipGetLastError() == hipSuccess ? MTBLX_OK : MTBLX_E_HIP;

@@ -122,12 +122,18 @@ struct RAcc<true> {
   uint32_t op = 0;
   uint64_t acc = 0, bad = 0;
 };
+struct RedV : Red {};   // the same with varint-coded values: the encoding is the kernel's template argument
 __device__ __forceinline__ const Red& red_of(const Red& r) { return r; }
+template <class... RD>
+struct IsVarint { static constexpr bool value = false; };
+template <>
+struct IsVarint<RedV> { static constexpr bool value = true; };
 
 // The plan walk, a kernel template on its trailing arguments.  k_scan_plan<> is the plan as it
 // always was, with the same kernel arguments.  k_scan_plan<Red> (mtblx_scan_reduce) also folds every
 // accepted record whose value is 8 * nf bytes long into the lanes' accumulators where the walk
-// counts it, and counts the others in nbad.
+// counts it, and counts the others in nbad.  k_scan_plan<RedV> does so for the values that are nf
+// varints back to back (reduce_ops.h, r_load_varint_lane).
 template <class... RD>
 __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
                                                    uint64_t idx_off, uint64_t idx_len, DecTab tab, const int32_t* type,
@@ -227,7 +233,11 @@ __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t
         vb += di.vlen;
         if constexpr (RED) {   // the value is db.d + [voff, voff + vlen), inside the block (checked above)
           const Red& rd = red_of(red...);
-          if (di.vlen != 8ull * rd.nf) {
+          if constexpr (IsVarint<RD...>::value) {
+            uint64_t x = 0;
+            if (!r_load_varint_lane<true>(db.d + di.voff, di.vlen, rd.nf, (uint32_t)lane, &x)) ++ra.bad;
+            else if ((uint32_t)lane < rd.nf) ra.acc = r_apply(ra.op, ra.acc, x);
+          } else if (di.vlen != 8ull * rd.nf) {
             ++ra.bad;
           } else if ((uint32_t)lane < rd.nf) {
             const uint8_t* vp = db.d + di.voff + 8u * (uint32_t)lane;   // any alignment
@@ -474,7 +484,8 @@ extern "C" int mtblx_scan_impl_plan(const uint8_t* file, uint64_t file_len, uint
                                 res, totals, ws, nullptr, nullptr, nullptr, s);
 }
 
-// spec == NULL: the plan alone.  Else k_scan_plan<Red> takes k_scan_plan<>'s place and fills fields / nbad.
+// spec == NULL: the plan alone.  Else k_scan_plan<Red> (k_scan_plan<RedV> for a varint spec) takes
+// k_scan_plan<>'s place and fills fields / nbad.
 extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
                                       uint64_t index_off, uint64_t index_len, const uint64_t* tab_start,
                                       const uint64_t* tab_doff, const uint64_t* tab_dlen, const int32_t* tab_st,
@@ -484,9 +495,10 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
                                       mtblx_scan_result* res, uint64_t* totals, void* ws, const mtblx_reduce* spec,
                                       uint64_t* fields, uint64_t* nbad, hipStream_t s) {
   using namespace mtblx_rd;
-  Red rd{};
+  RedV rd{};
+  bool varint = false;
   if (spec) {
-    if (!reduce_spec(spec, &rd.sp)) return MTBLX_E_INVAL;
+    if (!reduce_spec(spec, &rd.sp, &varint)) return MTBLX_E_INVAL;
     rd.nf = spec->nfields;
     rd.fields = fields;
     rd.nbad = nbad;
@@ -512,6 +524,14 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
                  k_scan_plan<>, dim3((unsigned)(need < cap ? need : cap)), dim3(256), 0, s, file, file_len, version,
                  verify, index_off, index_len, tab, dtype, keys, key_end, keys2, key2_end, max_records, max_blocks, nq,
                  wres, land);
+  else if (varint)
+    MTBLX_LAUNCH((MTBLX_R(file, file_len), MTBLX_R(tab.start, 8ull * ntab), MTBLX_R(tab.doff, 8ull * ntab),
+                  MTBLX_R(tab.dlen, 8ull * ntab), MTBLX_R(tab.st, 4ull * ntab), tab.dec, keys,
+                  MTBLX_R(key_end, 8ull * nq), keys2, MTBLX_R(key2_end, 8ull * nq), MTBLX_R(max_records, 8ull * nq),
+                  MTBLX_R(w, L.total), MTBLX_R(fields, 8ull * nq * rd.nf), MTBLX_R(nbad, 8ull * nq)),
+                 k_scan_plan<RedV>, dim3((unsigned)(need < cap ? need : cap)), dim3(256), 0, s, file, file_len, version,
+                 verify, index_off, index_len, tab, dtype, keys, key_end, keys2, key2_end, max_records, max_blocks, nq,
+                 wres, land, rd);
   else
     MTBLX_LAUNCH((MTBLX_R(file, file_len), MTBLX_R(tab.start, 8ull * ntab), MTBLX_R(tab.doff, 8ull * ntab),
                   MTBLX_R(tab.dlen, 8ull * ntab), MTBLX_R(tab.st, 4ull * ntab), tab.dec, keys,
@@ -519,7 +539,7 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
                   MTBLX_R(w, L.total), MTBLX_R(fields, 8ull * nq * rd.nf), MTBLX_R(nbad, 8ull * nq)),
                  k_scan_plan<Red>, dim3((unsigned)(need < cap ? need : cap)), dim3(256), 0, s, file, file_len, version,
                  verify, index_off, index_len, tab, dtype, keys, key_end, keys2, key2_end, max_records, max_blocks, nq,
-                 wres, land, rd);
+                 wres, land, static_cast<const Red&>(rd));
   MTBLX_LAUNCH((MTBLX_R(w, L.total), MTBLX_R(res, sizeof(mtblx_scan_result) * (uint64_t)nq)), k_scan_offsets, dim3(1),
                dim3(1024), 0, s, wres, res, nq, hdr, planned_mark(nq));
   if (hipGetLastError() != hipSuccess) return MTBLX_E_HIP;

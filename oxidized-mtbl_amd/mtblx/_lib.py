@@ -63,6 +63,7 @@ MERGE_MAX_SEGMENTS = 1 << 24                   # MTBLX_MERGE_MAX_SEGMENTS: segme
 MERGE_BADSEG = 4                               # totals[5] of mtblx_merge_seg_plan: a bad seg_off array
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)  # mtblx_reduce.op
 REDUCE_MAX_FIELDS = 8
+REDUCE_VARINT = 0x10                           # MTBLX_REDUCE_VARINT: OR-ed into every op, the fields are varints
 REDUCE_BADSEG = 8                              # *flags of mtblx_reduce_segments: a bad segment array
 REDUCE_MAX_SEGMENTS = 0xFFFFFF00               # MTBLX_REDUCE_MAX_SEGMENTS: nseg of mtblx_reduce_segments
 REDUCE_SEG_TILE = 1024                         # MTBLX_REDUCE_SEG_TILE: records per workgroup of mtblx_reduce_segments

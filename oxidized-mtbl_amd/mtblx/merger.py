@@ -90,8 +90,9 @@ def _records_list(r: DeviceRecords):
 def merge_records(sources, mode, stream=None, device=None):
     """One mtblx_merge_plan + mtblx_merge_emit over at most 64 sources (DeviceRecords, in source
     order) -> Grouped for "groups", else DeviceRecords.  `mode` is a name of MODES, or a Reduce (or
-    its shorthand name): then the emit is mtblx_merge_emit_reduce, with "first"'s layout, and a
-    group of two or more holding a value of another length raises MergeError.  Workspace and
+    its shorthand name): then the emit is mtblx_merge_emit_reduce, with "first"'s layout (a varint
+    Reduce: a layout of its own, inside "first"'s capacities), and a group of two or more holding a
+    bad value raises MergeError.  Workspace and
     outputs are allocated on the stream the kernels run on."""
     L = codec._require_device()
     if len(sources) > _lib.MERGE_MAX_SOURCES:
@@ -140,7 +141,7 @@ def merge_records(sources, mode, stream=None, device=None):
             raise RuntimeError(f"mtblx_merge_emit failed: {rc}")
         f = int(flags.item())   # synchronizes: the workspace may go back to the allocator after this
         if f & _lib.MERGE_BADVALUE:
-            raise MergeError(f"merge: a group of two or more holds a value that is not {red.width} bytes long")
+            raise MergeError(f"merge: a group of two or more holds a value that is not {red.shape}")
         if f:
             raise RuntimeError(f"mtblx_merge_emit: flags={f}")
         if m in (_lib.MERGE_FIRST, _lib.MERGE_LAST) and groups:   # vals was sized by its upper bound
@@ -241,7 +242,7 @@ def _merge_segments_64(sources, seg_offs, nseg, mode, s, dev):
             raise RuntimeError(f"mtblx_merge_seg_emit failed: {rc}")
         f = int(flags.item())   # synchronizes: the workspace may go back to the allocator after this
         if f & _lib.MERGE_BADVALUE:
-            raise MergeError(f"merge: a group of two or more holds a value that is not {red.width} bytes long")
+            raise MergeError(f"merge: a group of two or more holds a value that is not {red.shape}")
         if f:
             raise RuntimeError(f"mtblx_merge_seg_emit: flags={f}")
         if m in (_lib.MERGE_FIRST, _lib.MERGE_LAST) and groups:   # vals was sized by its upper bound

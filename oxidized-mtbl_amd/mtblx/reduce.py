@@ -1,8 +1,11 @@
-"""Device merge functions: u64 sum / min / max over fixed-width fields (include/mtblx.h "Device merge
-functions", csrc/reduce_dev.h).
+"""Device merge functions: u64 sum / min / max over fixed-width or varint-coded fields
+(include/mtblx.h "Device merge functions", csrc/reduce_dev.h).
 
     Reduce("sum")                    one little-endian u64 per value, added mod 2^64
     Reduce("sum", "min", "max")      24-byte values: (count, time_first, time_last)
+    Reduce("sum", "min", "max", encoding="varint")
+                                     the same record as three LEB128 varints back to back, the
+                                     convention of the mtbl ecosystem: decode, reduce, re-encode
     "sum_u64" | "min_u64" | "max_u64"   shorthands for one field
 
 A Reduce is accepted wherever the Merger and the Sorter accept "concat": the groups are then reduced
@@ -17,10 +20,19 @@ primitive, ``ReduceBatch`` the result of Reader.reduce_batch / Merger.reduce_bat
 As the reference never calls its merge function for a group of one (src/merger.rs:200-201,
 src/sorter.rs:166-167), a value alone in its group comes out unchanged whatever its length; in a
 group of two or more every value must be exactly 8 * nfields bytes long, else MergeError.
+
+With encoding="varint" a value is well-formed iff it is exactly nfields varints back to back as the
+reference's varint_decode64 (src/varint.rs:78-97) reads them: at most 10 bytes looked at per field, a
+field without a terminator among them (or before the value's end) is an error, as is an empty rest
+or a byte left over; non-canonical encodings are accepted and what a tenth byte holds above 2^64 is
+dropped.  The result is the reduced fields encoded canonically (varint_encode64), as long as they
+need: longer or shorter than any input.  Every other value is "bad": MergeError in a group of two
+or more, counted and left out by the aggregating scans.
 """
 from __future__ import annotations
 
 OPS = {"sum": 0, "min": 1, "max": 2}          # MTBLX_REDUCE_SUM / _MIN / _MAX
+ENCODINGS = {"u64le": 0, "varint": 0x10}       # OR-ed into every op: MTBLX_REDUCE_VARINT
 MAX_FIELDS = 8                                 # MTBLX_REDUCE_MAX_FIELDS
 SHORTHANDS = {"sum_u64": "sum", "min_u64": "min", "max_u64": "max"}
 _MASK = (1 << 64) - 1
@@ -28,13 +40,53 @@ _MASK = (1 << 64) - 1
 
 class MergeError(RuntimeError):
     """the merge function failed (the reference's Error::Merge): a group of two or more holds a
-    value that is not 8 * nfields bytes long (MTBLX_MERGE_BADVALUE)"""
+    value that is not 8 * nfields bytes long, or with encoding="varint" not nfields varints back to
+    back (MTBLX_MERGE_BADVALUE)"""
+
+
+def varint_encode(x: int) -> bytes:
+    """varint_encode64 (src/varint.rs:64-76): the canonical LEB128 bytes of a u64"""
+    out = bytearray()
+    while x >= 128:
+        out.append((x & 127) | 128)
+        x >>= 7
+    out.append(x)
+    return bytes(out)
+
+
+def varint_decode(data: bytes):
+    """varint_decode64 (src/varint.rs:78-97) on a non-empty slice -> (value, consumed); consumed == 0:
+    no terminator within the first 10 bytes (or before the slice's end)"""
+    x = 0
+    for j, b in enumerate(data[:10]):
+        x |= (b & 127) << (7 * j)
+        if not b & 128:
+            return x & _MASK, j + 1
+    return 0, 0
+
+
+def varint_fields(value: bytes, nfields: int):
+    """the fields of a well-formed varint-coded value, else None"""
+    out, p = [], 0
+    for _ in range(nfields):
+        if p >= len(value):
+            return None          # an empty rest: the reference would panic
+        x, k = varint_decode(value[p:])
+        if k == 0:
+            return None
+        out.append(x)
+        p += k
+    return out if p == len(value) else None
 
 
 class Reduce:
-    """1 to 8 fields, each an unsigned 64-bit little-endian integer with one op: "sum" | "min" | "max" """
+    """1 to 8 unsigned 64-bit fields, each with one op: "sum" | "min" | "max".  encoding: "u64le" (8
+    little-endian bytes per field) or "varint" (one LEB128 varint per field)"""
 
-    def __init__(self, *ops: str):
+    def __init__(self, *ops: str, encoding: str = "u64le"):
+        if encoding not in ENCODINGS:
+            raise ValueError(f"Reduce encoding: {encoding!r} (one of 'u64le', 'varint')")
+        self.encoding = encoding
         if not 1 <= len(ops) <= MAX_FIELDS:
             raise ValueError(f"Reduce takes 1 to {MAX_FIELDS} ops, not {len(ops)}")
         for op in ops:
@@ -43,17 +95,44 @@ class Reduce:
         self.ops = tuple(ops)
 
     @property
-    def width(self) -> int:
-        return 8 * len(self.ops)
+    def varint(self) -> bool:
+        return self.encoding == "varint"
+
+    @property
+    def width(self):
+        """the bytes of a value: 8 per field; None for varint-coded values, which have no one width"""
+        return None if self.varint else 8 * len(self.ops)
+
+    @property
+    def shape(self) -> str:
+        """what a value must be, for the error texts"""
+        if self.varint:
+            return f"{len(self.ops)} varints back to back"
+        return f"{self.width} bytes long"
 
     def __repr__(self):
-        return "Reduce(" + ", ".join(repr(o) for o in self.ops) + ")"
+        enc = ", encoding='varint'" if self.varint else ""
+        return "Reduce(" + ", ".join(repr(o) for o in self.ops) + enc + ")"
 
     def __eq__(self, other):
-        return isinstance(other, Reduce) and other.ops == self.ops
+        return isinstance(other, Reduce) and other.ops == self.ops and other.encoding == self.encoding
 
     def __hash__(self):
-        return hash(self.ops)
+        return hash((self.ops, self.encoding))
+
+    def decode(self, value):
+        """the fields of one value as unsigned ints, or None if the value is bad"""
+        if self.varint:
+            return varint_fields(value, len(self.ops))
+        if len(value) != self.width:
+            return None
+        return [int.from_bytes(value[8 * f: 8 * f + 8], "little") for f in range(len(self.ops))]
+
+    def encode(self, fields) -> bytes:
+        """the value that holds these fields (varint: canonical)"""
+        if self.varint:
+            return b"".join(varint_encode(int(x)) for x in fields)
+        return b"".join(int(x).to_bytes(8, "little") for x in fields)
 
     def cstruct(self):
         """the mtblx_reduce of this spec"""
@@ -61,22 +140,23 @@ class Reduce:
         r = _lib.ReduceSpec()
         r.nfields = len(self.ops)
         for f, op in enumerate(self.ops):
-            r.op[f] = OPS[op]
+            r.op[f] = OPS[op] | ENCODINGS[self.encoding]
         return r
 
     def host(self, key, values) -> bytes:
         """the same merge function on the host, as a callable(key, values) -> bytes would be given"""
-        w = self.width
+        rows = []
         for v in values:
-            if len(v) != w:
-                raise MergeError(f"merge: a value of {len(v)} bytes in a group of {len(values)}, {w} expected")
-        out = bytearray()
+            row = self.decode(v)
+            if row is None:
+                raise MergeError(f"merge: a value of {len(v)} bytes in a group of {len(values)} is not "
+                                 f"{self.shape}")
+            rows.append(row)
+        out = []
         for f, op in enumerate(self.ops):
-            xs = [int.from_bytes(v[8 * f: 8 * f + 8], "little") for v in values]
-            x = sum(xs) & _MASK if op == "sum" else min(xs) if op == "min" else max(xs)
-            out += x.to_bytes(8, "little")
-        return bytes(out)
-
+            xs = [row[f] for row in rows]
+            out.append(sum(xs) & _MASK if op == "sum" else min(xs) if op == "min" else max(xs))
+        return self.encode(out)
 
     def identities(self):
         """what a field is over nothing: 0 for "sum" and "max", 2^64 - 1 for "min" """
@@ -84,18 +164,19 @@ class Reduce:
 
     def fold(self, values):
         """The aggregating scans' semantics on the host: -> (fields, nrec, nbad).  nrec = len(values);
-        nbad = the values that are not exactly `width` bytes long, left out and counted; fields[f] =
+        nbad = the values that are not exactly `width` bytes long (varint: not well-formed), left out and
+        counted; fields[f] =
         op[f] over field f of the others (unsigned, "sum" mod 2^64), the op's identity over nothing."""
-        w = self.width
         acc = list(self.identities())
         nrec = nbad = 0
         for v in values:
             nrec += 1
-            if len(v) != w:
+            row = self.decode(v)
+            if row is None:
                 nbad += 1
                 continue
             for f, op in enumerate(self.ops):
-                x = int.from_bytes(v[8 * f: 8 * f + 8], "little")
+                x = row[f]
                 acc[f] = (acc[f] + x) & _MASK if op == "sum" else min(acc[f], x) if op == "min" else max(acc[f], x)
         return tuple(acc), nrec, nbad
 
@@ -171,7 +252,7 @@ def _signed(xs):
 class ReduceBatch:
     """Reader.reduce_batch's / Merger.reduce_batch's result.  Device tensors: `fields` int64 [nq, F]
     (the u64 bit patterns), `nrec` / `nbad` int64 [nq] (records yielded; those among them whose value
-    is not 8 * F bytes long, left out and counted), `status` int32 [nq] (SCAN_* of the scan walk).
+    is not 8 * F bytes long -- with a varint Reduce: not F varints --, left out and counted), `status` int32 [nq] (SCAN_* of the scan walk).
     A query the walk handed back (SCAN_LARGE, SCAN_FALLBACK, an irregular index) was answered by the
     seek path and its device records reduced by reduce_segments: values(q) / value_bytes(q) give every
     query's result, whichever path served it, and end(q) / err(q) how such a query's iteration ended
@@ -213,16 +294,17 @@ class ReduceBatch:
         return int(nr[q]), int(nb[q])
 
     def value_bytes(self, q: int):
-        """the 8 * F bytes of query q's fields, or None when nothing was reduced"""
+        """query q's fields as a value of the spec's encoding (8 * F bytes, or F canonical varints), or
+        None when nothing was reduced"""
         f, nr, nb = self._h()
         if int(nr[q]) - int(nb[q]) == 0:
             return None
-        return b"".join(int(x).to_bytes(8, "little") for x in f[q])
+        return self.reduce.encode(f[q])
 
     def check(self) -> None:
-        """MergeError if any query met a value that is not 8 * F bytes long"""
+        """MergeError if any query met a bad value (not 8 * F bytes long; varint: not F varints)"""
         nb = self._h()[2]
         if nb.any():
             q = int(nb.nonzero()[0][0])
-            raise MergeError(f"reduce_batch: query {q} met {int(nb[q])} values that are not {self.reduce.width} "
-                             "bytes long")
+            raise MergeError(f"reduce_batch: query {q} met {int(nb[q])} values that are not "
+                             f"{self.reduce.shape}")

@@ -90,7 +90,7 @@ def sort_records(recs: DeviceRecords, mode, stream=None):
             raise RuntimeError(f"mtblx_sort_emit failed: {rc}")
         f = int(flags.item())   # synchronizes: the workspace may go back to the allocator after this
         if f & _lib.MERGE_BADVALUE:
-            raise MergeError(f"merge: a group of two or more holds a value that is not {red.width} bytes long")
+            raise MergeError(f"merge: a group of two or more holds a value that is not {red.shape}")
         if f:
             raise RuntimeError(f"mtblx_sort_emit: flags={f}")
         if m in (_lib.MERGE_FIRST, _lib.MERGE_LAST) and groups:   # vals was sized by its upper bound
