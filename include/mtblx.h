@@ -45,7 +45,8 @@ extern "C" {
                                  mtblx_decode_blocks_valpos / mtblx_pipe_decode_valpos and with the
                                  mtblx_merge_*, mtblx_sort_*, mtblx_scan_* and mtblx_stage_* calls (the two
                                  mtblx_*_emit_reduce, mtblx_scan_reduce and mtblx_reduce_segments among
-                                 them): added symbols, no existing one changed */
+                                 them), and with mtblx_rollup_* and mtblx_reduce_encode: added symbols, no
+                                 existing one changed */
 
 /* ---- API return codes ---- */
 #define MTBLX_OK 0
@@ -890,6 +891,93 @@ int mtblx_scan_reduce(const uint8_t* file, uint64_t file_len, uint32_t version, 
 int mtblx_reduce_segments(const mtblx_records* recs, const uint64_t* seg_lo, const uint64_t* seg_hi, uint32_t nseg,
                           const mtblx_reduce* spec, uint64_t* fields, uint64_t* nbad, uint32_t* flags, void* stream);
 uint32_t mtblx_reduce_seg_tile(void);    /* MTBLX_REDUCE_SEG_TILE of the library that is loaded      */
+
+/* ---- Rollups: records grouped by a prefix of their key, one aggregate per group ----
+ * (csrc/rollup.hip, DESIGN.md §4 "Rollups").  The group key gkey(k) of a key k is given by an
+ * mtblx_group:
+ *    MTBLX_GROUP_LENGTH  k's first `length` bytes, or all of k if it is shorter (length >= 1);
+ *    MTBLX_GROUP_DELIM   k up to and including the `count`-th occurrence of the byte `delim`, or all
+ *                        of k if it holds fewer (delim <= 255, count >= 1).
+ * Both rules are monotone -- a <= b (unsigned bytes, then length) implies gkey(a) <= gkey(b) -- so over
+ * sorted keys the records of one group key are adjacent and the group keys come out strictly
+ * increasing.  Over one mtblx_records of n records with segments seg_off[0 .. nseg] (device u64,
+ * 0 = off[0] <= ... <= off[nseg] = n; nseg == 0: one segment that holds everything, seg_off is not
+ * read and seg_grp not written), record r is a HEAD iff r == 0, or r == seg_off[q] for some q, or
+ * gkey(r) differs from gkey(r - 1) in length or bytes.  A group is a head and the records up to the
+ * next head: groups are runs, as in uniq.  Nothing checks the order of the keys; on unsorted input
+ * equal group keys that are not adjacent stay apart.
+ *
+ * mtblx_rollup_plan (asynchronous) finds the heads and writes totals (DEVICE, 2 words, 8-byte aligned):
+ *    [0] groups   [1] the bytes of their keys
+ * which size the emit's outputs exactly.  mtblx_rollup_emit (asynchronous, same records, rule and
+ * segments) reads the planned workspace and writes, per group g in record order:
+ *    keys / key_end   gkey of the group (u64 END offsets: with a value per group an mtblx_records);
+ *    grp_rec[g]       its first record, and grp_rec[groups] = n: group g is the records
+ *                     [grp_rec[g], grp_rec[g + 1]), which is what mtblx_reduce_segments takes as
+ *                     seg_lo / seg_hi, and nrec[g] the difference;
+ *    seg_grp[q]       q = 0 .. nseg: the groups that begin before segment q; segment q's groups are
+ *                     [seg_grp[q], seg_grp[q + 1]), none for an empty segment.
+ * Every capacity is in BYTES.  *flags (device u32, cleared by the emit):
+ *    MTBLX_ROLLUP_OVERFLOW     a capacity is below what the totals ask for (keys: [1]; key_end: 8 * [0];
+ *                              grp_rec: 8 * ([0] + 1); seg_grp: 8 * (nseg + 1));
+ *    MTBLX_ROLLUP_NOT_PLANNED  the workspace is not that of a plan over this record count, segment
+ *                              count and rule;
+ *    MTBLX_ROLLUP_BADSEG       the plan met a seg_off that breaks its rule (its totals are then zero).
+ * With any of them set NOTHING else is written: the outputs are as they were.
+ * The workspace (device, 256-byte aligned, mtblx_rollup_workspace_bytes; no fill needed; one call at a
+ * time) holds a header, 9 B per record and 16 B per tile of mtblx_rollup_tile() records.
+ * n < MTBLX_MERGE_MAX_RECORDS; n == 0 is legal (no groups; grp_rec[0] = 0, seg_grp all 0).
+ * MTBLX_E_INVAL before any device call: NULL recs or group, an unknown kind, length == 0 (LENGTH),
+ * count == 0 or delim > 255 (DELIM), NULL or misaligned (256) workspace, ws_bytes too small, n too
+ * large, nseg above MTBLX_REDUCE_MAX_SEGMENTS, nseg != 0 with a NULL seg_off, n != 0 with a NULL
+ * key_end (keys may be NULL where every key is empty; vals and val_end are not read), key_end or
+ * seg_off not 8-byte aligned; the plan: NULL or misaligned totals; the emit: NULL out or flags
+ * (4-byte aligned), a NULL key_end or grp_rec, a NULL keys with a non-zero keys_cap, a NULL seg_grp
+ * with nseg != 0, and key_end, grp_rec or seg_grp not 8-byte aligned.
+ *
+ * The aggregate of a group is mtblx_reduce_segments over (grp_rec, grp_rec + 1): fields and nbad as
+ * the aggregating scans define them -- bad values left out and counted, nothing passes through, not
+ * even in a group of one.  mtblx_reduce_encode (asynchronous) then turns n rows of F = nfields u64
+ * words (device, 8-byte aligned: the fields of mtblx_reduce_segments) into n values and their u64 END
+ * offsets: row i's F words as little-endian bytes (val_end[i] = 8 * F * (i + 1)), or with
+ * MTBLX_REDUCE_VARINT as F canonical varints back to back (varint_encode64, src/varint.rs:64-76).
+ * cap (bytes of vals) must be at least 8 * F * n, with VARINT 10 * F * n: what n rows can take; the
+ * bytes used are val_end[n - 1].  The workspace (device, 8-byte aligned,
+ * mtblx_reduce_encode_workspace_bytes) holds one word per tile; the u64le form does not touch it.
+ * n == 0: MTBLX_OK, nothing written.  MTBLX_E_INVAL before any device call: a bad spec, n >=
+ * MTBLX_MERGE_MAX_RECORDS, and with n != 0 a NULL or misaligned fields / val_end / workspace, a NULL
+ * vals, a cap or ws_bytes too small. */
+#define MTBLX_GROUP_LENGTH 0
+#define MTBLX_GROUP_DELIM 1
+#define MTBLX_ROLLUP_OVERFLOW 1u
+#define MTBLX_ROLLUP_NOT_PLANNED 2u
+#define MTBLX_ROLLUP_BADSEG 8u
+typedef struct mtblx_group {
+  uint32_t kind;     /* MTBLX_GROUP_LENGTH / MTBLX_GROUP_DELIM                                          */
+  uint64_t length;   /* LENGTH: the bytes of a group key, >= 1                                          */
+  uint32_t delim;    /* DELIM: the delimiter byte, <= 255                                               */
+  uint32_t count;    /* DELIM: the group key ends with the count-th delimiter, >= 1                     */
+} mtblx_group;
+typedef struct mtblx_rolled {
+  uint8_t* keys;       /* device: key of group g = keys[key_end[g-1] .. key_end[g])                       */
+  uint64_t keys_cap;
+  uint64_t* key_end;   /* device [groups], u64 END offsets                                               */
+  uint64_t key_end_cap;
+  uint64_t* grp_rec;   /* device [groups + 1]: the first record of every group, then n                   */
+  uint64_t grp_rec_cap;
+  uint64_t* seg_grp;   /* device [nseg + 1]: the groups before every segment (nseg == 0: not written)    */
+  uint64_t seg_grp_cap;
+  uint32_t* flags;     /* device word, cleared by the call: MTBLX_ROLLUP_*                                */
+} mtblx_rolled;
+size_t mtblx_rollup_workspace_bytes(uint64_t nrec, uint32_t nseg);
+int mtblx_rollup_plan(const mtblx_records* recs, const mtblx_group* group, const uint64_t* seg_off, uint32_t nseg,
+                      uint64_t* totals, void* workspace, size_t ws_bytes, void* stream);
+int mtblx_rollup_emit(const mtblx_records* recs, const mtblx_group* group, const uint64_t* seg_off, uint32_t nseg,
+                      const mtblx_rolled* out, const void* workspace, size_t ws_bytes, void* stream);
+uint32_t mtblx_rollup_tile(void);        /* records per workgroup of the rollup's scans               */
+size_t mtblx_reduce_encode_workspace_bytes(uint64_t n);
+int mtblx_reduce_encode(const uint64_t* fields, uint64_t n, const mtblx_reduce* spec, uint8_t* vals,
+                        uint64_t* val_end, uint64_t cap, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- snappy raw decompression on the device (f4) ----
  * Reader::block's decompression step for CompressionType::Snappy (src/reader.rs:166-170 ->

@@ -31,10 +31,10 @@
 #include "mtblx.h"
 #include "bounds.h"
 #include "devinfo.h"
+#include "lane_dev.h"   // kThreads, block_scan, copy16, up256
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kTile = 1024;                 // handles per workgroup slice: 2 x 16 KiB of LDS, so
                                             // 5 workgroups (20 waves) fit a CU's 160 KiB
 constexpr int kPer = kTile / kThreads;      // records per thread in the grouping kernels
@@ -69,8 +69,6 @@ struct SrcTab {   // travels in the kernel arguments: 64 x 40 B + 65 x 4 B
   uint32_t nsrc;
 };
 
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-typedef uint32_t v4uu __attribute__((ext_vector_type(4), aligned(1)));
 typedef uint64_t u64u __attribute__((aligned(1)));
 
 struct Key {
@@ -301,29 +299,6 @@ __device__ __forceinline__ Contrib contrib(const SrcTab& t, const Handle* h, con
   return r;
 }
 
-// exclusive scan of one value per thread over the workgroup's 256 threads; total = the sum
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t* wsum, uint64_t* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned long long x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wsum[w] = x;
-  __syncthreads();
-  uint64_t base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kThreads / 64; ++k) {
-    const uint64_t s = wsum[k];
-    if (k < w) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + x - v;
-}
-
 __global__ void __launch_bounds__(kThreads) k_group_sums(SrcTab t, const Handle* h, const uint8_t* flag,
                                                          uint64_t* tiles, uint32_t n) {
   __shared__ uint64_t wsum[kThreads / 64];
@@ -426,34 +401,6 @@ __global__ void __launch_bounds__(kThreads) k_group_apply(SrcTab t, const Handle
 }
 
 // ---- emit ----
-// 16 lanes move len bytes: bytes up to the destination's 16-byte boundary, then 16-byte stores
-// (aligned loads where the source is aligned the same way, unaligned 16-byte loads elsewhere),
-// then the ragged end.  len == 0 falls through every step.
-__device__ __forceinline__ void copy16(uint8_t* d, const uint8_t* s, uint64_t len, uint32_t l) {
-  uint64_t head = (16u - (uint32_t)((uintptr_t)d & 15u)) & 15u;
-  if (head > len) head = len;
-  if (l < head) {
-    MTBLX_CHK(d + l, 1);
-    d[l] = s[l];
-  }
-  const uint64_t body = (len - head) >> 4;
-  const uint8_t* sb = s + head;
-  uint8_t* db = d + head;
-  const bool aligned = ((uintptr_t)sb & 15u) == 0;
-  for (uint64_t c = l; c < body; c += 16) {
-    v4u v;
-    if (aligned) v = *reinterpret_cast<const v4u*>(sb + 16 * c);
-    else v = *reinterpret_cast<const v4uu*>(sb + 16 * c);
-    MTBLX_CHK(db + 16 * c, 16);
-    *reinterpret_cast<v4u*>(db + 16 * c) = v;
-  }
-  const uint64_t done = head + 16 * body;
-  if (l < len - done) {
-    MTBLX_CHK(d + done + l, 1);
-    d[done + l] = s[done + l];
-  }
-}
-
 __global__ void __launch_bounds__(kThreads) k_merge_emit(SrcTab t, const uint64_t* hdr, const Handle* h,
                                                          const uint8_t* flag, GroupOut g, mtblx_merged o, int mode,
                                                          uint32_t n, uint64_t planned) {
@@ -541,8 +488,6 @@ struct Layout {
   size_t hdr, h0, h1, flag, gi, vi, koff, voff, foff, loff, tiles, edges, vtiles, total;
   uint32_t ntiles;
 };
-
-inline size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 
 Layout layout(uint64_t n) {
   Layout L{};

@@ -447,6 +447,78 @@ extern "C" int mtblx_reduce_segments(const mtblx_records* recs, const uint64_t* 
                                reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- rollups (csrc/rollup.hip): every argument is checked before any HIP call ----
+extern "C" size_t mtblx_rollup_impl_ws_bytes(uint64_t n);
+extern "C" int mtblx_rollup_impl_plan(const mtblx_records* recs, const mtblx_group* group, const uint64_t* seg_off,
+                                      uint32_t nseg, uint64_t* totals, void* ws, hipStream_t s);
+extern "C" int mtblx_rollup_impl_emit(const mtblx_records* recs, const mtblx_group* group, const uint64_t* seg_off,
+                                      uint32_t nseg, const mtblx_rolled* out, const void* ws, hipStream_t s);
+extern "C" size_t mtblx_reduce_encode_impl_ws_bytes(uint64_t n);
+extern "C" int mtblx_reduce_encode_impl(const uint64_t* fields, uint64_t n, const mtblx_reduce* spec, uint8_t* vals,
+                                        uint64_t* val_end, uint64_t cap, void* ws, hipStream_t s);
+
+extern "C" size_t mtblx_rollup_workspace_bytes(uint64_t nrec, uint32_t nseg) {
+  (void)nseg;   // the segments are read where the caller keeps them
+  return mtblx_rollup_impl_ws_bytes(nrec);
+}
+
+// what mtblx_rollup_plan and mtblx_rollup_emit check alike
+static int rollup_check(const mtblx_records* recs, const mtblx_group* g, const uint64_t* seg_off, uint32_t nseg,
+                        const void* ws, size_t wsb) {
+  if (!recs || !g) return MTBLX_E_INVAL;
+  if (g->kind == MTBLX_GROUP_LENGTH) {
+    if (g->length == 0) return MTBLX_E_INVAL;
+  } else if (g->kind == MTBLX_GROUP_DELIM) {
+    if (g->count == 0 || g->delim > 255u) return MTBLX_E_INVAL;
+  } else {
+    return MTBLX_E_INVAL;
+  }
+  if (recs->n >= MTBLX_MERGE_MAX_RECORDS || nseg > MTBLX_REDUCE_MAX_SEGMENTS) return MTBLX_E_INVAL;
+  if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0 || wsb < mtblx_rollup_impl_ws_bytes(recs->n))
+    return MTBLX_E_INVAL;
+  if (nseg && !seg_off) return MTBLX_E_INVAL;
+  if (recs->n && !recs->key_end) return MTBLX_E_INVAL;   // keys may be NULL where every key is empty
+  if ((reinterpret_cast<uintptr_t>(recs->key_end) | reinterpret_cast<uintptr_t>(seg_off)) & 7u) return MTBLX_E_INVAL;
+  return MTBLX_OK;
+}
+
+extern "C" int mtblx_rollup_plan(const mtblx_records* recs, const mtblx_group* group, const uint64_t* seg_off,
+                                 uint32_t nseg, uint64_t* totals, void* ws, size_t wsb, void* stream) {
+  if (!totals || (reinterpret_cast<uintptr_t>(totals) & 7u)) return MTBLX_E_INVAL;
+  const int c = rollup_check(recs, group, seg_off, nseg, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_rollup_impl_plan(recs, group, seg_off, nseg, totals, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mtblx_rollup_emit(const mtblx_records* recs, const mtblx_group* group, const uint64_t* seg_off,
+                                 uint32_t nseg, const mtblx_rolled* out, const void* ws, size_t wsb, void* stream) {
+  if (!out || !out->flags || (reinterpret_cast<uintptr_t>(out->flags) & 3u)) return MTBLX_E_INVAL;
+  if (!out->key_end || !out->grp_rec || (!out->keys && out->keys_cap) || (nseg && !out->seg_grp)) return MTBLX_E_INVAL;
+  if ((reinterpret_cast<uintptr_t>(out->key_end) | reinterpret_cast<uintptr_t>(out->grp_rec) |
+       reinterpret_cast<uintptr_t>(out->seg_grp)) & 7u)
+    return MTBLX_E_INVAL;
+  const int c = rollup_check(recs, group, seg_off, nseg, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_rollup_impl_emit(recs, group, seg_off, nseg, out, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" size_t mtblx_reduce_encode_workspace_bytes(uint64_t n) { return mtblx_reduce_encode_impl_ws_bytes(n); }
+
+extern "C" int mtblx_reduce_encode(const uint64_t* fields, uint64_t n, const mtblx_reduce* spec, uint8_t* vals,
+                                   uint64_t* val_end, uint64_t cap, void* ws, size_t wsb, void* stream) {
+  const int c = spec_check(spec);
+  if (c != MTBLX_OK) return c;
+  if (n >= MTBLX_MERGE_MAX_RECORDS) return MTBLX_E_INVAL;
+  if (n == 0) return MTBLX_OK;
+  const bool varint = spec->op[0] & MTBLX_REDUCE_VARINT;
+  if (!fields || !val_end || !vals || !ws) return MTBLX_E_INVAL;
+  if ((reinterpret_cast<uintptr_t>(fields) | reinterpret_cast<uintptr_t>(val_end) | reinterpret_cast<uintptr_t>(ws)) & 7u)
+    return MTBLX_E_INVAL;
+  if (cap < (varint ? 10ull : 8ull) * spec->nfields * n || wsb < mtblx_reduce_encode_impl_ws_bytes(n))
+    return MTBLX_E_INVAL;
+  return mtblx_reduce_encode_impl(fields, n, spec, vals, val_end, cap, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
 // ---- bounds-checked diagnostic build only (csrc/bounds.h, Makefile target `bounds`) ----
 #ifdef MTBLX_BOUNDS
 #include <stdio.h>

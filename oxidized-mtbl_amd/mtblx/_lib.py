@@ -51,6 +51,8 @@ EXPORTS = [
     "mtblx_encode_index_c",
     "mtblx_scan_workspace_bytes", "mtblx_scan_plan", "mtblx_scan_emit",
     "mtblx_scan_reduce", "mtblx_reduce_segments", "mtblx_reduce_seg_tile",
+    "mtblx_rollup_workspace_bytes", "mtblx_rollup_plan", "mtblx_rollup_emit", "mtblx_rollup_tile",
+    "mtblx_reduce_encode_workspace_bytes", "mtblx_reduce_encode",
     "mtblx_stage_workspace_bytes", "mtblx_stage_plan", "mtblx_stage_emit", "mtblx_scan_touch", "mtblx_bitmap_compact",
     "mtblx_table_gather", "mtblx_dir_ascends",
 ]
@@ -67,6 +69,8 @@ REDUCE_VARINT = 0x10                           # MTBLX_REDUCE_VARINT: OR-ed into
 REDUCE_BADSEG = 8                              # *flags of mtblx_reduce_segments: a bad segment array
 REDUCE_MAX_SEGMENTS = 0xFFFFFF00               # MTBLX_REDUCE_MAX_SEGMENTS: nseg of mtblx_reduce_segments
 REDUCE_SEG_TILE = 1024                         # MTBLX_REDUCE_SEG_TILE: records per workgroup of mtblx_reduce_segments
+GROUP_LENGTH, GROUP_DELIM = 0, 1                # mtblx_group.kind
+ROLLUP_OVERFLOW, ROLLUP_NOT_PLANNED, ROLLUP_BADSEG = 1, 2, 8   # *flags of mtblx_rollup_emit
 SORT_TILE = 1024                               # MTBLX_SORT_TILE: handles per tile-sorted run of mtblx_sort_plan
 PLAN_OUT_OF_ORDER, PLAN_PANIC, PLAN_TOO_LONG = 1, 2, 4
 SCAN_OK, SCAN_LARGE, SCAN_FALLBACK = range(3)  # mtblx_scan_result.status
@@ -100,6 +104,16 @@ class Merged(C.Structure):   # mtblx_merged (capacities in bytes)
 
 class ReduceSpec(C.Structure):   # mtblx_reduce
     _fields_ = [("nfields", C.c_uint32), ("op", C.c_uint8 * 8)]
+
+
+class Group(C.Structure):   # mtblx_group
+    _fields_ = [("kind", C.c_uint32), ("length", C.c_uint64), ("delim", C.c_uint32), ("count", C.c_uint32)]
+
+
+class Rolled(C.Structure):   # mtblx_rolled (capacities in bytes)
+    _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("key_end", C.c_void_p), ("key_end_cap", C.c_uint64),
+                ("grp_rec", C.c_void_p), ("grp_rec_cap", C.c_uint64), ("seg_grp", C.c_void_p),
+                ("seg_grp_cap", C.c_uint64), ("flags", C.c_void_p)]
 
 
 class ScanResult(C.Structure):   # mtblx_scan_result
@@ -355,6 +369,19 @@ def lib() -> C.CDLL:
                                             C.POINTER(ReduceSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mtblx_reduce_segments.restype = C.c_int
         L.mtblx_reduce_seg_tile.restype = C.c_uint32
+        _roll = [C.POINTER(Records), C.POINTER(Group), C.c_void_p, C.c_uint32]   # recs, group, seg_off, nseg
+        L.mtblx_rollup_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        L.mtblx_rollup_workspace_bytes.restype = C.c_size_t
+        L.mtblx_rollup_plan.argtypes = _roll + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_rollup_plan.restype = C.c_int
+        L.mtblx_rollup_emit.argtypes = _roll + [C.POINTER(Rolled), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_rollup_emit.restype = C.c_int
+        L.mtblx_rollup_tile.restype = C.c_uint32
+        L.mtblx_reduce_encode_workspace_bytes.argtypes = [C.c_uint64]
+        L.mtblx_reduce_encode_workspace_bytes.restype = C.c_size_t
+        L.mtblx_reduce_encode.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ReduceSpec), C.c_void_p, C.c_void_p,
+                                          C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_reduce_encode.restype = C.c_int
         L.mtblx_scan_emit.argtypes = _file + [C.c_uint64, C.c_uint64] + _tab + [
             C.c_uint32, C.POINTER(Scanned), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mtblx_scan_emit.restype = C.c_int

@@ -662,3 +662,44 @@ class Merger:
                 status[torch.tensor(sorted(mb._served), dtype=torch.int64, device=nrec.device)] = _lib.SCAN_FALLBACK
             ends = {q: (0, "None") for q in mb._served}   # a source's error has raised in scan_batch
             return ReduceBatch(red, fields, nrec, nbad, status, ends, mb.n_large, mb.n_fallback, s)
+
+    def rollup(self, group, reduce=None, stream=None):
+        """The merged stream rolled up: records() -- the Merger's own merge function joins each key's
+        values first, the empty-key quirk applied -- grouped by `group` (a rollup.GroupBy) with `reduce`
+        folded over every group's merged values -> rollup.Rollup with one segment, whose write_file()
+        gives the rolled-up .mtbl.  `reduce=None` takes the Merger's merge function when it is a
+        Reduce.  A callable merge function is refused.  Everything runs on `stream` (default:
+        Merger(stream=), else the current stream)."""
+        from .rollup import _as_group, rollup_records
+        grp, red = _as_group(group), self._rollup_reduce(reduce, "rollup")
+        s = self._s(stream)
+        with torch.cuda.stream(s):
+            recs = merge_all([_scan_records(r) for r in self.sources], self.merge, s, self._device())
+            return rollup_records(recs, grp, red, None, s)
+
+    def _rollup_reduce(self, reduce, what):
+        if callable(self.merge):
+            raise ValueError(f"{what}: a callable merge function leaves groups, not merged values")
+        red = as_reduce(reduce if reduce is not None else self.merge)
+        if red is None:
+            raise ValueError(f"{what}: pass a Reduce (the Merger's merge function is not one)" if reduce is None
+                             else f"{what}: {reduce!r} is not a Reduce")
+        return red
+
+    def rollup_batch(self, queries, group, reduce=None, max_blocks: int = 64, stream=None):
+        """Reader.rollup_batch over the merged view: scan_batch runs as it stands -- the Merger's own
+        merge function joins each key's values inside every query -- and one rollup over the merged
+        buffers with the queries as segments (seg_off = grp_off) groups the merged records of every
+        query; a query some source handed back is rolled up from its own merged device records.
+        `reduce=None` and a callable merge function as in rollup().  -> rollup.Rollup, groups(q) per
+        query.  Everything runs on `stream` (default: Merger(stream=), else the current stream)."""
+        from .rollup import _as_group, rollup_records
+        grp, red = _as_group(group), self._rollup_reduce(reduce, "rollup_batch")
+        mb = self.scan_batch(queries, max_blocks, None, stream)   # checks the queries before any source is touched
+        s = mb._stream
+        with torch.cuda.stream(s):
+            out = rollup_records(DeviceRecords(mb.keys, mb.key_end, mb.vals, mb.val_end), grp, red, mb.grp_off, s)
+            for q, r in mb._served.items():   # its slot in the buffers holds what the kernels left of it
+                out._served[q] = rollup_records(r, grp, red, None, s)
+                out._ends[q] = (0, "None")    # a source's error has raised in scan_batch
+            return out

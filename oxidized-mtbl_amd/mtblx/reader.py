@@ -1104,6 +1104,44 @@ class Reader:
             ends[q] = (sc.end, sc.err)
         return ReduceBatch(red, fields, nrec, nbad, status, ends, n_large, n_fallback, stream)
 
+    def rollup(self, group, reduce, stream=None):
+        """The whole file rolled up: its records (iter()) grouped by `group` (a rollup.GroupBy), `reduce`
+        folded over every group's values -> rollup.Rollup with one segment.  A file sorts its keys, so
+        the group keys increase strictly and Rollup.write_file() gives the rolled-up .mtbl.  A scan
+        that does not end cleanly raises as Merger sources do.  Everything runs on `stream` (default:
+        the current stream), which the call synchronises."""
+        from .merger import _clean_scan
+        from .rollup import rollup_records
+        stream = self._s(stream)
+        with torch.cuda.stream(stream):
+            return rollup_records(_clean_scan(self.iter()), group, reduce, None, stream)
+
+    def rollup_batch(self, queries, group, reduce, max_blocks: int = 64, stream=None):
+        """scan_batch, then one rollup over its records with the queries as segments (seg_off =
+        rec_off): per query, the records scan_batch reports for it grouped by `group` with `reduce`
+        folded over every group -> rollup.Rollup, groups(q) per query.  A query the walk hands back
+        (SCAN_LARGE, SCAN_FALLBACK) and every query of a reader with an irregular index is answered
+        by the seek path and rolled up from its own device records, kept beside the kernel path's
+        answer; end(q) / err(q) tell how such a query's iteration ended.  Everything runs on `stream`
+        (default: the current stream), which the call synchronises."""
+        from .encode import DeviceRecords
+        from .reduce import as_reduce
+        from .rollup import _as_group, rollup_records
+        grp = _as_group(group)
+        red = as_reduce(reduce)
+        if red is None:
+            raise ValueError(f"rollup_batch: {reduce!r} is not a Reduce")
+        stream = self._s(stream)
+        with torch.cuda.stream(stream):
+            sb = self._scan_batch(list(queries), max_blocks, None, stream)
+            out = rollup_records(DeviceRecords(sb.keys, sb.key_end, sb.vals, sb.val_end), grp, red, sb.rec_off, stream)
+            for q, sc in sb._served.items():
+                n = sc.nrec
+                out._served[q] = rollup_records(DeviceRecords(sc.keys, sc.key_end[:n], sc.vals, sc.val_end[:n]), grp,
+                                                red, None, stream)
+                out._ends[q] = (sc.end, sc.err)
+            return out
+
     def into_iter(self, kind: str = "iter", key: bytes = b"", key2: bytes = b""):
         """the stateful ReaderIntoIter (next() / seek()), see iterator.ReaderIntoIter"""
         from . import iterator
