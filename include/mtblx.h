@@ -842,6 +842,42 @@ int mtblx_merge_seg_plan_timed(const mtblx_records* src, const uint64_t* const* 
                                uint32_t nseg, uint64_t* totals, uint64_t* seg_end, void* workspace, size_t ws_bytes,
                                void* stream, float* phase_ms, uint32_t phase_cap);
 
+/* ---- Set operations: keep a key by which sources hold it (csrc/merge_dev.h k_group_select) ----
+ * A group of the Merger holds at most one record per source, so which sources hold its key is one
+ * 64-bit mask m: the OR of 1 << source over the group's records.  A selection keeps the group iff
+ *    (m & require) == require,  (m & exclude) == 0,  max(min_count, 1) <= popcount(m) <= max_count.
+ *    union                {0, 0, 1, 64}: the Merger as it is
+ *    intersection         require = all sources
+ *    difference A \ B...  require = 1 (A is source 0), exclude = the rest
+ *    in exactly one       max_count = 1 (two sources: the symmetric difference)
+ *    in at least k        min_count = k
+ *    semi-join            require = 0b11 with MTBLX_MERGE_FIRST: A's records whose key is in B
+ * The selection sees the groups the Merger yields: the empty-key quirk runs first, the records it
+ * drops contribute to no mask, and the item ("", [v]) that survives when only empty keys exist has
+ * the mask of the one source whose v it carries (the highest-numbered) and is selected like any
+ * other group.  The reference has no set operations; the definition above is the contract.
+ * mtblx_merge_plan_select / mtblx_merge_seg_plan_select are mtblx_merge_plan / mtblx_merge_seg_plan
+ * with `sel` applied between the grouping and the sums (sel == NULL: the plain plan).  totals is
+ * 8 words: [0..3] and [5] as in the plan, counting the kept groups and their records only, so they
+ * still size every emit mode exactly; [4] the records dropped by the empty-key quirk alone; [6] the
+ * groups the selection left out; [7] the records in those groups.  seg_end[q] counts kept groups.
+ * Workspace sizes and the planned mark are the plain plans': mtblx_merge_emit,
+ * mtblx_merge_emit_reduce, mtblx_merge_seg_emit and mtblx_merge_seg_emit_reduce take a
+ * select-planned workspace as they are.  MTBLX_E_INVAL before any device work: a bit at or above
+ * nsrc in require or exclude, require & exclude != 0, max_count == 0 or > 64,
+ * max(min_count, 1) > max_count, and everything the plain plans refuse. */
+typedef struct mtblx_select {
+  uint64_t require;    /* bit s: source s must hold the key                     */
+  uint64_t exclude;    /* bit s: source s must not hold the key                 */
+  uint32_t min_count;  /* sources holding the key: at least ... (0 reads as 1)  */
+  uint32_t max_count;  /* ... and at most (1..64)                               */
+} mtblx_select;
+int mtblx_merge_plan_select(const mtblx_records* src, uint32_t nsrc, const mtblx_select* sel, uint64_t* totals,
+                            void* workspace, size_t ws_bytes, void* stream);
+int mtblx_merge_seg_plan_select(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
+                                uint32_t nseg, const mtblx_select* sel, uint64_t* totals, uint64_t* seg_end,
+                                void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- Aggregating scans: a reduce spec folded over all the records a query matches ----
  * (csrc/scan.hip, csrc/reduce_seg.hip, DESIGN.md §4 "Aggregating scans").  The spec is the
  * mtblx_reduce of the device merge functions: F = nfields little-endian u64 fields, W = 8 * F (with

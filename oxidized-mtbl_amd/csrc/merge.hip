@@ -12,6 +12,8 @@
 //   k_merge_pass<SrcRuns>   ceil(log2 nsrc) launches, run 2j merged with run 2j+1, an unpaired run
 //                   carried over; the run boundaries come from the source table
 //   k_group_flags<true>, k_group_*   head flags, the empty-key quirk, six running sums
+//   k_group_select  (mtblx_merge_plan_select only) between the flags and the sums: the groups whose
+//                   source mask fails the rule are flagged out, and everything after works on the rest
 //   k_merge_emit    16 lanes per record gather the group's key once and the mode's values
 // The last three, with the handle and its order, are shared with the Sorter (sort.hip) and live in
 // merge_dev.h, which describes them.
@@ -81,13 +83,24 @@ uint64_t planned_mark(uint64_t n, uint32_t nsrc) { return kMagic ^ n ^ ((uint64_
 
 extern "C" size_t mtblx_merge_impl_ws_bytes(uint64_t nrec) { return layout(nrec).total; }
 
+// the argument check of the two *_plan_select calls (mtblx_api.cpp): needs no device
+extern "C" int mtblx_merge_impl_select_ok(const mtblx_select* sel, uint32_t nsrc) {
+  mtblx_select rule;
+  return select_rule(sel, nsrc, &rule) ? 1 : 0;
+}
+
 // arguments already checked (mtblx_api.cpp): ws 256-byte aligned and large enough, nsrc <= 64
 // phase_ms (diagnostic, may be NULL): HIP-event times of [0] the handle build (prefix, handles, order
 // check), [1 .. passes] the merge passes, [passes + 1] the grouping; phase_cap >= passes + 2
-extern "C" int mtblx_merge_impl_plan(const mtblx_records* src, uint32_t nsrc, uint64_t* totals, void* ws,
-                                     hipStream_t s, float* phase_ms, uint32_t phase_cap) {
+// sel (may be NULL: no selection, totals is 6 words): the rule of mtblx_merge_plan_select, totals 8 words
+extern "C" int mtblx_merge_impl_plan(const mtblx_records* src, uint32_t nsrc, const mtblx_select* sel,
+                                     uint64_t* totals, void* ws, hipStream_t s, float* phase_ms,
+                                     uint32_t phase_cap) {
   PhaseEvents ev(phase_ms != nullptr);
   if (phase_ms && phase_cap < passes_for(nsrc) + 2) return MTBLX_E_INVAL;
+  mtblx_select rule{};
+  if (sel && !select_rule(sel, nsrc, &rule)) return MTBLX_E_INVAL;
+  const int nt = sel ? 8 : 6;
   SrcTab t;
   const uint64_t n64 = fill_tab(src, nsrc, &t);
   if (n64 == UINT64_MAX) return MTBLX_E_INVAL;
@@ -112,7 +125,7 @@ extern "C" int mtblx_merge_impl_plan(const mtblx_records* src, uint32_t nsrc, ui
         hipStreamSynchronize(s) != hipSuccess)
       return MTBLX_E_HIP;
     if (host[H_FLAGS] & MTBLX_MERGE_UNSORTED) {
-      memset(totals, 0, 6 * sizeof(uint64_t));
+      memset(totals, 0, nt * sizeof(uint64_t));
       totals[5] = host[H_FLAGS];
       return MTBLX_E_FORMAT;
     }
@@ -124,10 +137,16 @@ extern "C" int mtblx_merge_impl_plan(const mtblx_records* src, uint32_t nsrc, ui
       ev.mark(s);
     }
     const Handle* hf = hb[np & 1];
-    MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_flags<true>, dim3((unsigned)want), b, 0, s, t, hdr, hf, flag, n);
+    // with a selection the flags go to the gi array first (unwritten until k_group_apply) and
+    // k_group_select reads them there: its workgroups read their neighbours' records
+    uint8_t* fin = sel ? w + L.gi : flag;
+    MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_flags<true>, dim3((unsigned)want), b, 0, s, t, hdr, hf, fin, n);
+    if (sel) MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_select, dim3(L.ntiles), b, 0, s, hf, fin, flag,
+                          reinterpret_cast<uint64_t*>(w + L.edges), n, rule);
     MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_sums, dim3(L.ntiles), b, 0, s, t, hf, flag, tiles, n);
   }
-  MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_scan, dim3(1), b, 0, s, hdr, tiles, L.ntiles, n, planned_mark(n, nsrc));
+  MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_scan, dim3(1), b, 0, s, hdr, tiles, L.ntiles, n, planned_mark(n, nsrc),
+               sel && n ? reinterpret_cast<const uint64_t*>(w + L.edges) : nullptr);
   if (n) {
     MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_apply, dim3(L.ntiles), b, 0, s, t, hb[passes_for(nsrc) & 1], flag,
                  tiles, group_out(w, L), n);
@@ -139,6 +158,10 @@ extern "C" int mtblx_merge_impl_plan(const mtblx_records* src, uint32_t nsrc, ui
     return MTBLX_E_HIP;
   if (phase_ms) ev.read(phase_ms, phase_cap);
   for (int i = 0; i < 6; ++i) totals[i] = host[i];
+  if (sel) {
+    totals[6] = host[H_SELGROUPS];
+    totals[7] = host[H_SELRECS];
+  }
   if (host[H_FLAGS] & MTBLX_MERGE_UNSORTED) return MTBLX_E_FORMAT;
   if (host[H_FLAGS] & MTBLX_MERGE_INTERNAL) return MTBLX_E_HIP;
   return MTBLX_OK;

@@ -15,7 +15,9 @@
 //                   running sums (groups, key bytes, values, value bytes, first-value bytes,
 //                   last-value bytes) as a three-launch scan: tile sums, one workgroup over the
 //                   tile sums, apply
-//   k_merge_emit    16 lanes per record gather the group's key once and the mode's values
+//   k_group_select  set operations (the merge and the segmented merge, on request): between the
+//                   flags and the sums, the groups whose source mask fails a rule are flagged out
+//   k_merge_emit   16 lanes per record gather the group's key once and the mode's values
 //
 // Order: keys compare as unsigned bytes then by length (Vec<u8>::cmp); equal keys by source number,
 // then by record index.  The order is total, so no pass ever reorders equal keys: run 2j holds
@@ -49,6 +51,7 @@ constexpr uint64_t kSortMagic = 0x5354424c58535254ull;
 // workspace header words (u64)
 enum { H_GROUPS = 0, H_KEYB, H_NVAL, H_VALB, H_DROPPED, H_FLAGS, H_SKIP, H_PLANNED, H_FIRSTB, H_LASTB,
        H_SEGSKIP,   // merge_seg.hip: u64 words from the header to the per-segment skip array
+       H_SELGROUPS, H_SELRECS,   // the groups a selection (k_group_select) left out, the records in them
        H_WORDS = 32 };
 constexpr int kReduceEdgeWords = 18;   // u64 words per tile of the device merge functions' edge array (reduce_dev.h)
 // k_merge_emit's internal mode, after the public MTBLX_MERGE_* ones: the last step of the varint reduce
@@ -242,7 +245,8 @@ __global__ void __launch_bounds__(kThreads) k_merge_pass(SrcTab t, uint64_t* hdr
 }
 
 // ---- grouping ----
-// flag[i]: bit 0 = record i (merged order) starts a group, bit 1 = dropped by the empty-key quirk.
+// flag[i]: bit 0 = record i (merged order) starts a group, bit 1 = dropped by the empty-key quirk
+// (or, later, left out by k_group_select: every kernel after it skips both alike).
 // MergerIter::next (src/merger.rs:182-186) uses cur_key.is_empty() for "no current key": every
 // empty-key record re-adopts the next heap entry's key and clears cur_vals, so the empty-key
 // records (at most one per sorted source: the first ones in merged order) vanish when any record
@@ -273,6 +277,155 @@ __global__ void __launch_bounds__(kThreads) k_group_flags(SrcTab t, uint64_t* hd
   }
   MTBLX_CHK(flag + i, 1);
   flag[i] = (uint8_t)((head ? 1 : 0) | (dropped ? 2 : 0));
+}
+
+// ---- selection (set operations; include/mtblx.h "Set operations") ----
+// A group (a kept head and the kept non-heads after it) holds at most one record per source, so its
+// membership is one 64-bit mask and it is never longer than 64 records.  k_group_select keeps the
+// groups whose mask passes the rule and gives every record of the others bit 1; a rejected head
+// keeps bit 0, because contrib(), k_merge_emit and the reducers find a group's tail as
+// flag[i + 1] & 1 and the kept group in front of a rejected one must still see its end.  Records the
+// quirk dropped belong to no group and pass through.
+// One launch: a workgroup owns kTile records and stages their flags and source bits with a halo of
+// 63 records on each side in LDS (a group of a tile's record lies inside it), the "bit 0" bits as a
+// bitmap (a ballot per 64 records), from which a record finds its group's first and last record with
+// one clz / ctz.  Six doubling steps of a segmented OR leave every group's mask with its last record,
+// which evaluates the rule once; every member reads the verdict there.  The input flags are read
+// from `fin`, a copy apart from `flag` (the plans let the flag kernels write into the gi array,
+// unused until k_group_apply): a workgroup reads its neighbours' records in the halo while they write.
+// What a tile leaves out (groups, records) goes to two words per tile of `part` (the reducers' edge
+// array, unused until an emit), which k_group_scan adds up: no two workgroups write one address.
+constexpr int kSelHalo = MTBLX_MERGE_MAX_SOURCES - 1;
+constexpr int kSelWin = kTile + 2 * 64;     // the tile and the two halos, padded to whole bitmap words
+constexpr int kSelWords = kSelWin / 64;
+constexpr int kSelPer = (kSelWin + kThreads - 1) / kThreads;
+static_assert(kSelWin % 64 == 0 && kSelHalo < 64 && kThreads % 64 == 0, "a wave's ballot is one bitmap word");
+
+// the first record of p's run: the last window position <= p whose bit is set
+__device__ __forceinline__ uint32_t sel_first(const uint64_t* bnd, uint32_t p) {
+  const uint32_t w = p >> 6;
+  const uint64_t x = bnd[w] & (~0ull >> (63u - (p & 63u)));
+  if (x) return (w << 6) + 63u - (uint32_t)__builtin_clzll(x);
+  if (w && bnd[w - 1]) return ((w - 1) << 6) + 63u - (uint32_t)__builtin_clzll(bnd[w - 1]);
+  return p > (uint32_t)kSelHalo ? p - kSelHalo : 0u;   // a run cut by the window's edge (halo records only)
+}
+
+// the last record of p's run: the position before the first one > p whose bit is set
+__device__ __forceinline__ uint32_t sel_last(const uint64_t* bnd, uint32_t p) {
+  const uint32_t q = p + 1;
+  if (q >= (uint32_t)kSelWin) return p;
+  const uint32_t w = q >> 6;
+  const uint64_t x = bnd[w] >> (q & 63u);
+  if (x) return q + (uint32_t)__builtin_ctzll(x) - 1u;
+  if (w + 1 < (uint32_t)kSelWords && bnd[w + 1]) return ((w + 1) << 6) + (uint32_t)__builtin_ctzll(bnd[w + 1]) - 1u;
+  return p + kSelHalo < (uint32_t)kSelWin ? p + kSelHalo : (uint32_t)kSelWin - 1u;
+}
+
+// sel.min_count >= 1 (the host has normalised it).  The Sorter has no sources and never launches it
+[[maybe_unused]] __global__ void __launch_bounds__(kThreads)
+k_group_select(const Handle* h, const uint8_t* fin, uint8_t* flag, uint64_t* part, uint32_t n, mtblx_select sel) {
+  __shared__ uint64_t m[2][kSelWin];
+  __shared__ uint64_t bnd[kSelWords];
+  __shared__ uint8_t fl[kSelWin], rej[kSelWin];
+  __shared__ uint32_t cnt[2];
+  const uint64_t lo = (uint64_t)blockIdx.x * kTile;
+  const uint64_t hi = lo + kTile < n ? lo + kTile : n;
+  const uint64_t wlo = lo >= (uint64_t)kSelHalo ? lo - kSelHalo : 0;
+  const uint64_t whi = hi + kSelHalo < n ? hi + kSelHalo : n;
+  if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+#pragma unroll
+  for (int it = 0; it < kSelPer; ++it) {
+    const uint32_t p = threadIdx.x + it * kThreads;
+    if (p >= (uint32_t)kSelWin) break;   // the same for a whole wave
+    const uint64_t rec = wlo + p;
+    uint8_t f = 3;   // past the window: not kept, and the end of whatever run reaches it
+    uint64_t mk = 0;
+    if (rec < whi) {
+      MTBLX_CHK(fin + rec, 1);
+      f = fin[rec];
+      if (!(f & 2)) {
+        MTBLX_CHK(&h[rec].src, 4);
+        mk = 1ull << (h[rec].src & 63u);
+      }
+    }
+    fl[p] = f;
+    rej[p] = 0;
+    m[0][p] = mk;
+    const uint64_t b = __ballot(f & 1);
+    if ((threadIdx.x & 63u) == 0) bnd[p >> 6] = b;
+  }
+  __syncthreads();
+  uint32_t first[kSelPer], last[kSelPer];
+#pragma unroll
+  for (int it = 0; it < kSelPer; ++it) {
+    const uint32_t p = threadIdx.x + it * kThreads;
+    first[it] = last[it] = 0;
+    if (p < (uint32_t)kSelWin) {
+      first[it] = sel_first(bnd, p);
+      last[it] = sel_last(bnd, p);
+    }
+  }
+  int cur = 0;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {   // the inclusive segmented OR: 64 records in six steps
+#pragma unroll
+    for (int it = 0; it < kSelPer; ++it) {
+      const uint32_t p = threadIdx.x + it * kThreads;
+      if (p < (uint32_t)kSelWin) {
+        uint64_t v = m[cur][p];
+        if (p >= first[it] + d) v |= m[cur][p - d];
+        m[cur ^ 1][p] = v;
+      }
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+#pragma unroll
+  for (int it = 0; it < kSelPer; ++it) {   // the rule, once per group: by its last record
+    const uint32_t p = threadIdx.x + it * kThreads;
+    if (p < (uint32_t)kSelWin && last[it] == p && !(fl[p] & 2)) {
+      const uint64_t g = m[cur][p];
+      const uint32_t c = (uint32_t)__popcll(g);
+      const bool keep = (g & sel.require) == sel.require && !(g & sel.exclude) && c >= sel.min_count &&
+                        c <= sel.max_count;
+      rej[p] = keep ? 0 : 1;
+    }
+  }
+  __syncthreads();
+  const uint32_t t0 = (uint32_t)(lo - wlo), t1 = (uint32_t)(hi - wlo);   // the tile inside the window
+#pragma unroll
+  for (int it = 0; it < kSelPer; ++it) {
+    const uint32_t p = threadIdx.x + it * kThreads;
+    if (p >= (uint32_t)kSelWin) break;   // the same for a whole wave
+    const bool mine = p >= t0 && p < t1;
+    const uint8_t f = fl[p];
+    const bool out = mine && !(f & 2) && rej[last[it]];
+    if (mine) {
+      MTBLX_CHK(flag + wlo + p, 1);
+      flag[wlo + p] = (uint8_t)(out ? f | 2 : f);
+    }
+    const uint64_t recs = __ballot(out), heads = __ballot(out && (f & 1));
+    if ((threadIdx.x & 63u) == 0 && recs) {
+      atomicAdd(&cnt[0], (uint32_t)__popcll(heads));
+      atomicAdd(&cnt[1], (uint32_t)__popcll(recs));
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    MTBLX_CHK(part + 2ull * blockIdx.x + threadIdx.x, 8);
+    part[2ull * blockIdx.x + threadIdx.x] = cnt[threadIdx.x];
+  }
+}
+
+// The rule as k_group_select takes it (min_count 0 reads as 1), or false: a bit at or above nsrc, a
+// source both required and excluded, max_count outside 1..64, max(min_count, 1) > max_count
+inline bool select_rule(const mtblx_select* sel, uint32_t nsrc, mtblx_select* out) {
+  const uint64_t all = nsrc >= 64 ? ~0ull : (1ull << nsrc) - 1;
+  const uint32_t mn = sel->min_count ? sel->min_count : 1u;
+  if (((sel->require | sel->exclude) & ~all) || (sel->require & sel->exclude)) return false;
+  if (sel->max_count == 0 || sel->max_count > MTBLX_MERGE_MAX_SOURCES || mn > sel->max_count) return false;
+  *out = mtblx_select{sel->require, sel->exclude, mn, sel->max_count};
+  return true;
 }
 
 struct Contrib {
@@ -321,13 +474,24 @@ __global__ void __launch_bounds__(kThreads) k_group_sums(SrcTab t, const Handle*
   }
 }
 
-// one workgroup: the tile sums -> their exclusive prefixes (in place), the totals, the planned mark
+// one workgroup: the tile sums -> their exclusive prefixes (in place), the totals, the planned mark.
+// selpart (NULL: no selection ran): k_group_select's two words per tile, added up into the header
 __global__ void __launch_bounds__(kThreads) k_group_scan(uint64_t* hdr, uint64_t* tiles, uint32_t ntiles, uint32_t n,
-                                                         uint64_t planned) {
+                                                         uint64_t planned, const uint64_t* selpart) {
   __shared__ uint64_t wsum[kThreads / 64];
   uint64_t carry[kChan] = {};
+  uint64_t left[2] = {};   // the groups a selection left out, the records in them
   for (uint32_t b = 0; b < ntiles; b += kThreads) {
     const uint32_t i = b + threadIdx.x;
+    if (selpart) {   // the same for the whole workgroup
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        if (i < ntiles) MTBLX_CHK(selpart + 2ull * i + q, 8);
+        uint64_t tot;
+        (void)block_scan(i < ntiles ? selpart[2ull * i + q] : 0, wsum, &tot);
+        left[q] += tot;
+      }
+    }
 #pragma unroll
     for (int q = 0; q < kChan; ++q) {
       if (i < ntiles) MTBLX_CHK(tiles + (uint64_t)i * kChan + q, 8);
@@ -344,7 +508,9 @@ __global__ void __launch_bounds__(kThreads) k_group_scan(uint64_t* hdr, uint64_t
     hdr[H_KEYB] = carry[1];
     hdr[H_NVAL] = carry[2];
     hdr[H_VALB] = carry[3];
-    hdr[H_DROPPED] = (uint64_t)n - carry[2];
+    hdr[H_DROPPED] = (uint64_t)n - carry[2] - left[1];   // the quirk's drops alone
+    hdr[H_SELGROUPS] = left[0];
+    hdr[H_SELRECS] = left[1];
     hdr[H_FIRSTB] = carry[4];
     hdr[H_LASTB] = carry[5];
     hdr[H_PLANNED] = planned;

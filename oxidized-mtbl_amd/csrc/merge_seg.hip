@@ -23,6 +23,8 @@
 //   k_seg_pos     one thread per segment: the first merged handle of a later segment
 //   k_seg_strip   src &= 63: from here on the handles are the Merger's, and k_group_sums / _scan /
 //                 _apply, k_merge_emit and the reduce kernels run as they are
+//   k_group_select  (mtblx_merge_seg_plan_select only) after k_seg_strip, when the source is back in
+//                 0..63: a group never spans a segment, so the Merger's selection runs as it is
 //   k_seg_ends    seg_end[q] = the groups before that handle
 // No kernel waits for another workgroup: the launches are ordered by the stream.
 #include <hip/hip_runtime.h>
@@ -251,11 +253,15 @@ extern "C" size_t mtblx_merge_seg_impl_ws_bytes(uint64_t nrec, uint32_t nseg) { 
 // nseg <= MTBLX_MERGE_MAX_SEGMENTS, no NULL seg_off entry.  phase_ms (diagnostic, may be NULL):
 // [0] the offsets' check, the skips, the handles, [1 .. passes] the merge passes, [passes + 1] the
 // grouping and the segment ends; phase_cap >= passes + 2
+// sel (may be NULL: no selection, totals is 6 words): the rule of mtblx_merge_seg_plan_select, totals 8 words
 extern "C" int mtblx_merge_seg_impl_plan(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
-                                         uint32_t nseg, uint64_t* totals, uint64_t* seg_end, void* ws, hipStream_t s,
-                                         float* phase_ms, uint32_t phase_cap) {
+                                         uint32_t nseg, const mtblx_select* sel, uint64_t* totals, uint64_t* seg_end,
+                                         void* ws, hipStream_t s, float* phase_ms, uint32_t phase_cap) {
   PhaseEvents ev(phase_ms != nullptr);
   if (phase_ms && phase_cap < passes_for(nsrc) + 2) return MTBLX_E_INVAL;
+  mtblx_select rule{};
+  if (sel && !select_rule(sel, nsrc, &rule)) return MTBLX_E_INVAL;
+  const int nt = sel ? 8 : 6;
   SrcTab t;
   SegTab g;
   const uint64_t n64 = fill_tab(src, nsrc, &t);
@@ -291,7 +297,7 @@ extern "C" int mtblx_merge_seg_impl_plan(const mtblx_records* src, const uint64_
         hipStreamSynchronize(s) != hipSuccess)
       return MTBLX_E_HIP;
     if (host[H_FLAGS] & (MTBLX_MERGE_BADSEG | MTBLX_MERGE_UNSORTED)) {
-      memset(totals, 0, 6 * sizeof(uint64_t));
+      memset(totals, 0, nt * sizeof(uint64_t));
       totals[5] = host[H_FLAGS];
       return MTBLX_E_FORMAT;
     }
@@ -303,13 +309,18 @@ extern "C" int mtblx_merge_seg_impl_plan(const mtblx_records* src, const uint64_
                    hb[(p + 1) & 1], n, p);
       ev.mark(s);
     }
-    MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_seg_flags, dim3(blocks_for(n)), b, 0, s, t, hdr, hf, flag, n);
+    // with a selection the flags go to the gi array first (unwritten until k_group_apply) and
+    // k_group_select reads them there: its workgroups read their neighbours' records
+    uint8_t* fin = sel ? w + L.gi : flag;
+    MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_seg_flags, dim3(blocks_for(n)), b, 0, s, t, hdr, hf, fin, n);
     if (nseg) MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_seg_pos, dim3(blocks_for(nseg)), b, 0, s, hf, pos, n, nseg);
     MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_seg_strip, dim3(blocks_for(n)), b, 0, s, hf, n);
+    if (sel) MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_group_select, dim3(L.ntiles), b, 0, s, hf, fin, flag,
+                          reinterpret_cast<uint64_t*>(w + L.edges), n, rule);
     MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_group_sums, dim3(L.ntiles), b, 0, s, t, hf, flag, tiles, n);
   }
   MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_group_scan, dim3(1), b, 0, s, hdr, tiles, L.ntiles, n,
-               planned_mark(n, nsrc, nseg));
+               planned_mark(n, nsrc, nseg), sel && n ? reinterpret_cast<const uint64_t*>(w + L.edges) : nullptr);
   if (n) {
     MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_group_apply, dim3(L.ntiles), b, 0, s, t, hf, flag, tiles, go, n);
     if (nseg)
@@ -325,6 +336,10 @@ extern "C" int mtblx_merge_seg_impl_plan(const mtblx_records* src, const uint64_
     return MTBLX_E_HIP;
   if (phase_ms) ev.read(phase_ms, phase_cap);
   for (int i = 0; i < 6; ++i) totals[i] = host[i];
+  if (sel) {
+    totals[6] = host[H_SELGROUPS];
+    totals[7] = host[H_SELRECS];
+  }
   if (host[H_FLAGS] & MTBLX_MERGE_UNSORTED) return MTBLX_E_FORMAT;
   if (host[H_FLAGS] & MTBLX_MERGE_INTERNAL) return MTBLX_E_HIP;
   return MTBLX_OK;

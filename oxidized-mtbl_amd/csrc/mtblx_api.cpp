@@ -103,8 +103,10 @@ extern "C" int mtblx_decode_blocks_verify(const mtblx_block_batch* in, const mtb
 
 // ---- Merger (csrc/merge.hip): the argument checks need no device ----
 extern "C" size_t mtblx_merge_impl_ws_bytes(uint64_t nrec);
-extern "C" int mtblx_merge_impl_plan(const mtblx_records* src, uint32_t nsrc, uint64_t* totals, void* ws,
-                                     hipStream_t s, float* phase_ms, uint32_t phase_cap);
+extern "C" int mtblx_merge_impl_plan(const mtblx_records* src, uint32_t nsrc, const mtblx_select* sel,
+                                     uint64_t* totals, void* ws, hipStream_t s, float* phase_ms,
+                                     uint32_t phase_cap);
+extern "C" int mtblx_merge_impl_select_ok(const mtblx_select* sel, uint32_t nsrc);
 extern "C" int mtblx_merge_impl_emit(const mtblx_records* src, uint32_t nsrc, int mode, const mtblx_merged* out,
                                      const void* ws, hipStream_t s);
 
@@ -126,12 +128,23 @@ static int merge_check(const mtblx_records* src, uint32_t nsrc, const void* ws, 
   return MTBLX_OK;
 }
 
+// sel == NULL: mtblx_merge_plan itself (totals[6] and [7] are 0: nothing was left out)
+extern "C" int mtblx_merge_plan_select(const mtblx_records* src, uint32_t nsrc, const mtblx_select* sel,
+                                       uint64_t* totals, void* ws, size_t wsb, void* stream) {
+  if (!totals) return MTBLX_E_INVAL;
+  if (sel && (nsrc > MTBLX_MERGE_MAX_SOURCES || !mtblx_merge_impl_select_ok(sel, nsrc))) return MTBLX_E_INVAL;
+  const int c = merge_check(src, nsrc, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  totals[6] = totals[7] = 0;
+  return mtblx_merge_impl_plan(src, nsrc, sel, totals, ws, reinterpret_cast<hipStream_t>(stream), nullptr, 0);
+}
+
 extern "C" int mtblx_merge_plan(const mtblx_records* src, uint32_t nsrc, uint64_t* totals, void* ws, size_t wsb,
                                 void* stream) {
   if (!totals) return MTBLX_E_INVAL;
   const int c = merge_check(src, nsrc, ws, wsb);
   if (c != MTBLX_OK) return c;
-  return mtblx_merge_impl_plan(src, nsrc, totals, ws, reinterpret_cast<hipStream_t>(stream), nullptr, 0);
+  return mtblx_merge_impl_plan(src, nsrc, nullptr, totals, ws, reinterpret_cast<hipStream_t>(stream), nullptr, 0);
 }
 
 extern "C" int mtblx_merge_plan_timed(const mtblx_records* src, uint32_t nsrc, uint64_t* totals, void* ws, size_t wsb,
@@ -139,7 +152,8 @@ extern "C" int mtblx_merge_plan_timed(const mtblx_records* src, uint32_t nsrc, u
   if (!totals || !phase_ms) return MTBLX_E_INVAL;
   const int c = merge_check(src, nsrc, ws, wsb);
   if (c != MTBLX_OK) return c;
-  return mtblx_merge_impl_plan(src, nsrc, totals, ws, reinterpret_cast<hipStream_t>(stream), phase_ms, phase_cap);
+  return mtblx_merge_impl_plan(src, nsrc, nullptr, totals, ws, reinterpret_cast<hipStream_t>(stream), phase_ms,
+                               phase_cap);
 }
 
 extern "C" int mtblx_merge_emit(const mtblx_records* src, uint32_t nsrc, int mode, const mtblx_merged* out,
@@ -246,8 +260,8 @@ extern "C" int mtblx_sort_emit_reduce(const mtblx_records* in, const mtblx_reduc
 // ---- segmented merge (csrc/merge_seg.hip): the argument checks need no device ----
 extern "C" size_t mtblx_merge_seg_impl_ws_bytes(uint64_t nrec, uint32_t nseg);
 extern "C" int mtblx_merge_seg_impl_plan(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
-                                         uint32_t nseg, uint64_t* totals, uint64_t* seg_end, void* ws, hipStream_t s,
-                                         float* phase_ms, uint32_t phase_cap);
+                                         uint32_t nseg, const mtblx_select* sel, uint64_t* totals, uint64_t* seg_end,
+                                         void* ws, hipStream_t s, float* phase_ms, uint32_t phase_cap);
 extern "C" int mtblx_merge_seg_impl_emit(const mtblx_records* src, uint32_t nsrc, uint32_t nseg, int mode,
                                          const mtblx_reduce* spec, const mtblx_merged* out, void* ws, hipStream_t s);
 
@@ -278,8 +292,8 @@ extern "C" int mtblx_merge_seg_plan_timed(const mtblx_records* src, const uint64
   if (!totals || !phase_ms || (nseg && !seg_end)) return MTBLX_E_INVAL;
   const int c = merge_seg_check(src, seg_off, nsrc, nseg, ws, wsb);
   if (c != MTBLX_OK) return c;
-  return mtblx_merge_seg_impl_plan(src, seg_off, nsrc, nseg, totals, seg_end, ws, reinterpret_cast<hipStream_t>(stream),
-                                   phase_ms, phase_cap);
+  return mtblx_merge_seg_impl_plan(src, seg_off, nsrc, nseg, nullptr, totals, seg_end, ws,
+                                   reinterpret_cast<hipStream_t>(stream), phase_ms, phase_cap);
 }
 
 extern "C" int mtblx_merge_seg_plan(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
@@ -288,8 +302,21 @@ extern "C" int mtblx_merge_seg_plan(const mtblx_records* src, const uint64_t* co
   if (!totals || (nseg && !seg_end)) return MTBLX_E_INVAL;
   const int c = merge_seg_check(src, seg_off, nsrc, nseg, ws, wsb);
   if (c != MTBLX_OK) return c;
-  return mtblx_merge_seg_impl_plan(src, seg_off, nsrc, nseg, totals, seg_end, ws, reinterpret_cast<hipStream_t>(stream),
-                                   nullptr, 0);
+  return mtblx_merge_seg_impl_plan(src, seg_off, nsrc, nseg, nullptr, totals, seg_end, ws,
+                                   reinterpret_cast<hipStream_t>(stream), nullptr, 0);
+}
+
+// sel == NULL: mtblx_merge_seg_plan itself (totals[6] and [7] are 0: nothing was left out)
+extern "C" int mtblx_merge_seg_plan_select(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,
+                                           uint32_t nseg, const mtblx_select* sel, uint64_t* totals,
+                                           uint64_t* seg_end, void* ws, size_t wsb, void* stream) {
+  if (!totals || (nseg && !seg_end)) return MTBLX_E_INVAL;
+  if (sel && (nsrc > MTBLX_MERGE_MAX_SOURCES || !mtblx_merge_impl_select_ok(sel, nsrc))) return MTBLX_E_INVAL;
+  const int c = merge_seg_check(src, seg_off, nsrc, nseg, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  totals[6] = totals[7] = 0;
+  return mtblx_merge_seg_impl_plan(src, seg_off, nsrc, nseg, sel, totals, seg_end, ws,
+                                   reinterpret_cast<hipStream_t>(stream), nullptr, 0);
 }
 
 extern "C" int mtblx_merge_seg_emit(const mtblx_records* src, const uint64_t* const* seg_off, uint32_t nsrc,

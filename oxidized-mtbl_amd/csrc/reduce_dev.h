@@ -236,7 +236,10 @@ __global__ void __launch_bounds__(kThreads) k_reduce_tile(SrcTab t, const uint64
   if (threadIdx.x == kThreads - 1) {   // acc: the whole tile (the threads past n bring nothing)
     const uint64_t last = (tile0 + kTile < n ? tile0 + kTile : (uint64_t)n) - 1;
     const bool has = acc.fl & 1u;
-    const bool open = has && last + 1 < n && !(flag[last + 1] & 1);
+    // the next record goes on with the trail's group iff it is a kept non-head.  A record flagged
+    // out (bit 1) without the head bit is no member of it: after a selection (k_group_select) the
+    // later records of a rejected group can follow the trail's tail across the tile's edge
+    const bool open = has && last + 1 < n && !(flag[last + 1] & 3);
     uint32_t m = has ? 1u : 0u;
     if (has) {
       m |= open ? 4u : 0u;

@@ -162,7 +162,8 @@ extern "C" int mtblx_sort_impl_plan(const mtblx_records* in, uint64_t* totals, v
     MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_flags<false>, dim3((unsigned)want), b, 0, s, t, hdr, hf, flag, n);
     MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_sums, dim3(L.ntiles), b, 0, s, t, hf, flag, tiles, n);
   }
-  MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_scan, dim3(1), b, 0, s, hdr, tiles, L.ntiles, n, sort_mark(n));
+  MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_scan, dim3(1), b, 0, s, hdr, tiles, L.ntiles, n, sort_mark(n),
+               nullptr);
   if (n) {
     MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_group_apply, dim3(L.ntiles), b, 0, s, t, hf, flag, tiles, group_out(w, L), n);
   }

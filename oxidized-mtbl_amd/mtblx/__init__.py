@@ -9,12 +9,16 @@ Package layout
               Merger.scan_batch / get_batch: batched reads of the merged view (csrc/merge_seg.hip)
   sorter.py   Sorter / SorterBuilder mirror of src/sorter.rs over the device sort (csrc/sort.hip)
   reduce.py   Reduce / MergeError: u64 sum / min / max merge functions evaluated on the device (csrc/reduce_dev.h)
+  setops.py   Select / diff_files: set operations on the Merger, a key kept by which sources hold it
+              (csrc/merge_dev.h k_group_select)
   rollup.py   GroupBy / rollup_records / Rollup: records grouped by a key prefix, one aggregate per group
               (csrc/rollup.hip); Reader.rollup / rollup_batch and Merger.rollup / rollup_batch sit on it
 """
 from ._lib import EXPORTS, LIB_PATH, lib  # noqa: F401
 from .reduce import MergeError, Reduce, ReduceBatch, reduce_segments  # noqa: F401
 from .rollup import GroupBy, Rollup, reduce_encode, rollup_records  # noqa: F401
+from . import setops  # noqa: F401
+from .setops import Select  # noqa: F401
 from .writer import CompressionType, OutOfOrderKey, Writer, WriterBuilder  # noqa: F401
 
 
@@ -29,5 +33,5 @@ def __getattr__(name):   # Merger / MergerBuilder / Sorter / SorterBuilder need 
 
 
 __all__ = ["Writer", "WriterBuilder", "CompressionType", "OutOfOrderKey", "Merger", "MergerBuilder", "Sorter", "SorterBuilder",
-           "MergedScanBatch", "merge_segments",
+           "MergedScanBatch", "merge_segments", "Select", "setops",
            "Reduce", "MergeError", "GroupBy", "Rollup", "rollup_records", "reduce_encode", "lib", "LIB_PATH", "EXPORTS"]

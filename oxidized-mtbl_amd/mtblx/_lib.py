@@ -47,6 +47,7 @@ EXPORTS = [
     "mtblx_merge_emit_reduce", "mtblx_sort_emit_reduce",
     "mtblx_merge_seg_workspace_bytes", "mtblx_merge_seg_plan", "mtblx_merge_seg_emit", "mtblx_merge_seg_emit_reduce",
     "mtblx_merge_seg_plan_timed",
+    "mtblx_merge_plan_select", "mtblx_merge_seg_plan_select",
     "mtblx_snappy_compress_workspace_bytes", "mtblx_snappy_slots", "mtblx_snappy_compress_dev", "mtblx_frame_blocks",
     "mtblx_encode_index_c",
     "mtblx_scan_workspace_bytes", "mtblx_scan_plan", "mtblx_scan_emit",
@@ -100,6 +101,11 @@ class Merged(C.Structure):   # mtblx_merged (capacities in bytes)
     _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("key_end", C.c_void_p), ("key_end_cap", C.c_uint64),
                 ("vals", C.c_void_p), ("vals_cap", C.c_uint64), ("val_end", C.c_void_p), ("val_end_cap", C.c_uint64),
                 ("grp_end", C.c_void_p), ("grp_end_cap", C.c_uint64), ("flags", C.c_void_p)]
+
+
+class SelectSpec(C.Structure):   # mtblx_select
+    _fields_ = [("require", C.c_uint64), ("exclude", C.c_uint64), ("min_count", C.c_uint32),
+                ("max_count", C.c_uint32)]
 
 
 class ReduceSpec(C.Structure):   # mtblx_reduce
@@ -354,6 +360,12 @@ def lib() -> C.CDLL:
         L.mtblx_merge_seg_emit_reduce.argtypes = _seg + [C.POINTER(ReduceSpec), C.POINTER(Merged), C.c_void_p,
                                                          C.c_size_t, C.c_void_p]
         L.mtblx_merge_seg_emit_reduce.restype = C.c_int
+        L.mtblx_merge_plan_select.argtypes = [C.POINTER(Records), C.c_uint32, C.POINTER(SelectSpec), u64p, C.c_void_p,
+                                              C.c_size_t, C.c_void_p]
+        L.mtblx_merge_plan_select.restype = C.c_int
+        L.mtblx_merge_seg_plan_select.argtypes = _seg + [C.POINTER(SelectSpec), u64p, C.c_void_p, C.c_void_p,
+                                                         C.c_size_t, C.c_void_p]
+        L.mtblx_merge_seg_plan_select.restype = C.c_int
         L.mtblx_scan_workspace_bytes.argtypes = [C.c_uint32]
         L.mtblx_scan_workspace_bytes.restype = C.c_size_t
         _file = [C.c_void_p, C.c_uint64, C.c_uint32]                                    # file, file_len, version

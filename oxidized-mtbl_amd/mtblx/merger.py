@@ -24,6 +24,14 @@ iter_range / get on a merger source, for a whole batch): Merger.scan_batch / sca
 get_batch take Reader.scan_batch on every source and join the answers with ONE segmented merge
 (merge_segments over mtblx_merge_seg_plan / mtblx_merge_seg_emit, csrc/merge_seg.hip): order
 (query, key, source), the empty-key quirk applied inside every query.  -> MergedScanBatch.
+
+Set operations (setops.Select; include/mtblx.h "Set operations"): ``select=`` on merge_records /
+merge_all / merge_segments, MergerBuilder.select(sel) and Merger(..., select=sel) keep a key by which
+sources hold it (mtblx_merge_plan_select / mtblx_merge_seg_plan_select); every Merger method then
+works on the selected groups.  Refused with ValueError before any device work: a selection over
+more than 64 sources (a rule over source masks cannot be applied per round), a selection together
+with max_records (m + 1 records per source no longer cover the first m items once groups are
+dropped), a Select naming a source that is not there.
 """
 from __future__ import annotations
 
@@ -36,6 +44,7 @@ import torch
 from . import _lib, codec, encode
 from .encode import DeviceRecords
 from .reduce import MergeError, Reduce, ReduceBatch, as_reduce, check_merge, reduce_segments  # noqa: F401
+from .setops import Select, as_select  # noqa: F401
 from .writer import CompressionType
 
 MODES = {"groups": _lib.MERGE_GROUPS, "concat": _lib.MERGE_CONCAT, "first": _lib.MERGE_FIRST,
@@ -87,16 +96,18 @@ def _records_list(r: DeviceRecords):
     return out
 
 
-def merge_records(sources, mode, stream=None, device=None):
+def merge_records(sources, mode, stream=None, device=None, select=None):
     """One mtblx_merge_plan + mtblx_merge_emit over at most 64 sources (DeviceRecords, in source
     order) -> Grouped for "groups", else DeviceRecords.  `mode` is a name of MODES, or a Reduce (or
     its shorthand name): then the emit is mtblx_merge_emit_reduce, with "first"'s layout (a varint
     Reduce: a layout of its own, inside "first"'s capacities), and a group of two or more holding a
-    bad value raises MergeError.  Workspace and
+    bad value raises MergeError.  `select` (a setops.Select): only the groups it keeps come out
+    (mtblx_merge_plan_select).  Workspace and
     outputs are allocated on the stream the kernels run on."""
     L = codec._require_device()
     if len(sources) > _lib.MERGE_MAX_SOURCES:
         raise ValueError("merge_records takes at most 64 sources (Merger merges in rounds)")
+    select = as_select(select, len(sources))
     red = as_reduce(mode)
     m = _lib.MERGE_FIRST if red is not None else MODES[mode]
     dev = torch.device(device) if device is not None else (sources[0].key_end.device if sources else
@@ -114,9 +125,13 @@ def merge_records(sources, mode, stream=None, device=None):
         wsb = int(L.mtblx_merge_workspace_bytes(n, nsrc))
         ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
         wp = (ws.data_ptr() + 255) & ~255
-        tot = (C.c_uint64 * 6)()
+        tot = (C.c_uint64 * 8)()
         sh = C.c_void_p(int(s.cuda_stream))
-        rc = L.mtblx_merge_plan(arr, nsrc, tot, C.c_void_p(wp), wsb, sh)
+        if select is not None:
+            sel = select.cstruct()
+            rc = L.mtblx_merge_plan_select(arr, nsrc, C.byref(sel), tot, C.c_void_p(wp), wsb, sh)
+        else:
+            rc = L.mtblx_merge_plan(arr, nsrc, tot, C.c_void_p(wp), wsb, sh)
         if rc == _lib.MTBLX_E_FORMAT:
             raise UnsortedSource(int(tot[5]))
         if rc != 0:
@@ -171,11 +186,13 @@ def _regroup(parts, stream):
         return Grouped(va.keys, va.key_end, va.vals, torch.cumsum(lens, 0), vb.val_end // 8, stream)
 
 
-def merge_all(sources, mode, stream=None, device=None):
+def merge_all(sources, mode, stream=None, device=None, select=None):
     """merge_records over any number of sources: rounds of 64 with the same mode, which keeps
     source order (and with it the exact result) for every mode; a Reduce is associative and
-    passes a group of one through, so applying it per round gives the same bytes too."""
+    passes a group of one through, so applying it per round gives the same bytes too.  `select`
+    needs one round: at most 64 sources."""
     sources = list(sources)
+    select = as_select(select, len(sources))
     grouped = mode == "groups"
     first = True
     dev = torch.device(device) if device is not None else (sources[0].key_end.device if sources else None)
@@ -186,12 +203,12 @@ def merge_all(sources, mode, stream=None, device=None):
         if grouped and not first:
             sources = [_regroup(c, stream) for c in chunks]
         else:
-            sources = [merge_records(c, mode, stream, device) for c in chunks]
+            sources = [merge_records(c, mode, stream, device, select) for c in chunks]
         first = False
     return sources[0]
 
 
-def _merge_segments_64(sources, seg_offs, nseg, mode, s, dev):
+def _merge_segments_64(sources, seg_offs, nseg, mode, s, dev, select=None):
     """one mtblx_merge_seg_plan + emit over at most 64 sources -> (DeviceRecords | Grouped, seg_end)"""
     L = codec._require_device()
     red = as_reduce(mode)
@@ -213,9 +230,15 @@ def _merge_segments_64(sources, seg_offs, nseg, mode, s, dev):
         ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
         wp = (ws.data_ptr() + 255) & ~255
         seg_end = torch.empty(nseg, dtype=torch.int64, device=dev)
-        tot = (C.c_uint64 * 6)()
+        tot = (C.c_uint64 * 8)()
         sh = C.c_void_p(int(s.cuda_stream))
-        rc = L.mtblx_merge_seg_plan(arr, offs, nsrc, nseg, tot, C.c_void_p(seg_end.data_ptr()), C.c_void_p(wp), wsb, sh)
+        if select is not None:
+            sel = select.cstruct()
+            rc = L.mtblx_merge_seg_plan_select(arr, offs, nsrc, nseg, C.byref(sel), tot, C.c_void_p(seg_end.data_ptr()),
+                                               C.c_void_p(wp), wsb, sh)
+        else:
+            rc = L.mtblx_merge_seg_plan(arr, offs, nsrc, nseg, tot, C.c_void_p(seg_end.data_ptr()), C.c_void_p(wp), wsb,
+                                        sh)
         if rc == _lib.MTBLX_E_FORMAT:
             if int(tot[5]) & _lib.MERGE_BADSEG:
                 raise ValueError("merge_segments: a seg_off array is not 0 = off[0] <= ... <= off[nseg] = n")
@@ -274,7 +297,7 @@ def _regroup_segments(parts, seg_ends, nseg, s, dev):
         return Grouped(va.keys, va.key_end, va.vals, torch.cumsum(lens, 0), vb.val_end // 8, s), se
 
 
-def merge_segments(sources, seg_offs, mode, stream=None, device=None):
+def merge_segments(sources, seg_offs, mode, stream=None, device=None, select=None):
     """The merge_records of the segmented calls (mtblx_merge_seg_plan / _emit, csrc/merge_seg.hip).
     Source i (a DeviceRecords) is nseg sorted runs back to back, cut by seg_offs[i] (device int64
     [nseg + 1], 0 = off[0] <= ... <= off[nseg] = n); segment q of the result is the Merger's result
@@ -282,10 +305,13 @@ def merge_segments(sources, seg_offs, mode, stream=None, device=None):
     MODES or a Reduce, as in merge_records.  -> (Grouped for "groups", else DeviceRecords; seg_end:
     device int64 [nseg], the END group index of every segment).  Any number of sources: rounds of 64
     with the same mode, a round's output cut by its seg_end being a source of the next ("groups":
-    the two-CONCAT regrouping of _regroup, segmented)."""
+    the two-CONCAT regrouping of _regroup, segmented).  `select` (a setops.Select, at most 64
+    sources): every segment holds the groups it keeps, and seg_end counts those
+    (mtblx_merge_seg_plan_select)."""
     sources, seg_offs = list(sources), list(seg_offs)
     if len(sources) != len(seg_offs):
         raise ValueError("merge_segments: one seg_off tensor per source")
+    select = as_select(select, len(sources))
     if not sources and device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     dev = torch.device(device) if device is not None else seg_offs[0].device
@@ -304,7 +330,7 @@ def merge_segments(sources, seg_offs, mode, stream=None, device=None):
                 if grouped and not first:
                     outs.append(_regroup_segments(c, [x[1:] for x in o], nseg, s, dev))
                 else:
-                    outs.append(_merge_segments_64(c, o, nseg, mode, s, dev))
+                    outs.append(_merge_segments_64(c, o, nseg, mode, s, dev, select))
             sources = [r for r, _ in outs]
             seg_offs = [_seg_off_of(se) for _, se in outs]
             first = False
@@ -500,6 +526,7 @@ class MergerBuilder:
     def __init__(self, merge):
         self._merge = check_merge(merge)
         self._sources = []
+        self._select = None
 
     def add(self, source) -> "MergerBuilder":
         self.push(source)
@@ -512,15 +539,21 @@ class MergerBuilder:
         self._sources.extend(sources)
         return self
 
+    def select(self, sel) -> "MergerBuilder":
+        """keep a key by which sources hold it (a setops.Select over the sources in the order added)"""
+        self._select = sel
+        return self
+
     def build(self) -> "Merger":
-        return Merger(list(self._sources), self._merge)
+        return Merger(list(self._sources), self._merge, select=self._select)
 
 
 class Merger:
-    def __init__(self, sources, merge, stream=None):
+    def __init__(self, sources, merge, stream=None, select=None):
         self.sources = sources
         self.merge = check_merge(merge)
         self.stream = stream
+        self.select = as_select(select, len(sources))   # every method below works on the groups it keeps
 
     @staticmethod
     def builder(merge) -> MergerBuilder:
@@ -536,7 +569,7 @@ class Merger:
     def _run(self, mode: str):
         s = self._s()
         with torch.cuda.stream(s):   # the sources are scanned on the stream that merges them
-            return merge_all([_scan_records(r) for r in self.sources], mode, s, self._device())
+            return merge_all([_scan_records(r) for r in self.sources], mode, s, self._device(), self.select)
 
     def groups(self) -> Grouped:
         """MultiIter's items, on the device"""
@@ -584,6 +617,11 @@ class Merger:
     # ---- batched reads of the merged view ----
     def _scan_merge(self, queries, max_blocks, max_records, stream, mode) -> MergedScanBatch:
         qs, limits = check_queries(queries, max_records)
+        if self.select is not None:
+            as_select(self.select, len(self.sources))
+            if any(m is not None for m in limits):
+                raise ValueError("scan_batch: max_records cannot be combined with a selection (m + 1 records per "
+                                 "source do not cover the first m items once groups are dropped)")
         s = self._s(stream)
         with torch.cuda.stream(s):   # the sources' scans, the seek-path answers, the merges and the read-back: all on s
             return self._scan_merge_on(qs, limits, max_blocks, s, mode)
@@ -601,8 +639,8 @@ class Merger:
         offs = [sb.rec_off.contiguous() for sb in sbs]
         if not sbs:   # no sources: nq empty segments of one empty source
             recs, offs = [DeviceRecords.from_list([], device=dev)], [torch.zeros(nq + 1, dtype=torch.int64, device=dev)]
-        merged, seg_end = merge_segments(recs, offs, mode, s, dev)
-        served = {q: _cut_groups(merge_all(parts[q], mode, s, dev), limits[q]) for q in back}
+        merged, seg_end = merge_segments(recs, offs, mode, s, dev, self.select if sbs else None)
+        served = {q: _cut_groups(merge_all(parts[q], mode, s, dev, self.select), limits[q]) for q in back}
         return MergedScanBatch(nq, merged, seg_end, limits, served, self.merge, sbs, s)
 
     def scan_batch(self, queries, max_blocks: int = 64, max_records=None, stream=None) -> MergedScanBatch:
@@ -674,7 +712,7 @@ class Merger:
         grp, red = _as_group(group), self._rollup_reduce(reduce, "rollup")
         s = self._s(stream)
         with torch.cuda.stream(s):
-            recs = merge_all([_scan_records(r) for r in self.sources], self.merge, s, self._device())
+            recs = merge_all([_scan_records(r) for r in self.sources], self.merge, s, self._device(), self.select)
             return rollup_records(recs, grp, red, None, s)
 
     def _rollup_reduce(self, reduce, what):
