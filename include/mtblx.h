@@ -45,8 +45,8 @@ extern "C" {
                                  mtblx_decode_blocks_valpos / mtblx_pipe_decode_valpos and with the
                                  mtblx_merge_*, mtblx_sort_*, mtblx_scan_* and mtblx_stage_* calls (the two
                                  mtblx_*_emit_reduce, mtblx_scan_reduce and mtblx_reduce_segments among
-                                 them), and with mtblx_rollup_* and mtblx_reduce_encode: added symbols, no
-                                 existing one changed */
+                                 them), with mtblx_rollup_* and mtblx_reduce_encode and with mtblx_where_*:
+                                 added symbols, no existing one changed */
 
 /* ---- API return codes ---- */
 #define MTBLX_OK 0
@@ -1014,6 +1014,103 @@ uint32_t mtblx_rollup_tile(void);        /* records per workgroup of the rollup'
 size_t mtblx_reduce_encode_workspace_bytes(uint64_t n);
 int mtblx_reduce_encode(const uint64_t* fields, uint64_t n, const mtblx_reduce* spec, uint8_t* vals,
                         uint64_t* val_end, uint64_t cap, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- Value predicates: records kept or dropped by the fields of their value ----
+ * (csrc/where.hip, DESIGN.md §4 "Value predicates").  An mtblx_where is a value layout -- exactly that
+ * of an mtblx_reduce: F = nfields little-endian u64 fields (the value is exactly 8 * F bytes), or with
+ * MTBLX_WHERE_VARINT F varints back to back, read with every quirk listed under "Varint-coded values"
+ * above -- plus at most one inclusive, unsigned range per field.  For one value:
+ *    a value that is not well-formed under the layout is BAD: its record is dropped and counted,
+ *      never kept and never an error;
+ *    otherwise field f PASSES iff (lo[f] <= x_f && x_f <= hi[f]) != (bit f of outside);
+ *    flags without MTBLX_WHERE_ANY: kept iff every field of `mask` passes (mask == 0: always kept);
+ *    with MTBLX_WHERE_ANY:          kept iff some field of `mask` passes (mask == 0: never kept).
+ * lo > hi is legal and is an empty range (with its outside bit: every value).  The reference has no
+ * predicates; the definition above is the contract.  MTBLX_E_INVAL before any device work: nfields 0
+ * or above MTBLX_REDUCE_MAX_FIELDS, unknown flag bits, a mask or outside bit at or above nfields,
+ * outside & ~mask.
+ *
+ * mtblx_where_plan (SYNCHRONOUS) evaluates the predicate once per record of `recs`, leaves the
+ * keep / bad bits in the workspace and writes
+ *    totals (HOST, 6 words)  [0] kept records  [1] their key bytes  [2] their value bytes
+ *                            [3] bad values    [4] well-formed values rejected    [5] flags
+ *    seg_end[q]  (device [nseg]) the END index of segment q in the kept order: segment q's kept
+ *                records are [seg_end[q - 1], seg_end[q]) (0 before segment 0);
+ *    seg_bad[q]  (device [nseg], may be NULL) the bad values in segment q.
+ * seg_off (device u64 [nseg + 1], 0 = off[0] <= ... <= off[nseg] = n) is checked on the device before
+ * it indexes anything: a bad array gives MTBLX_E_FORMAT with MTBLX_WHERE_BADSEG in totals[5] (the
+ * other totals 0; seg_end / seg_bad as they were).  nseg == 0: the whole of recs, no segments;
+ * seg_off, seg_end and seg_bad are not read or written.
+ * mtblx_where_emit (asynchronous, same records) reads the planned workspace and writes the kept
+ * records in their order: keys / key_end / vals / val_end (u64 END offsets: an mtblx_records as it
+ * stands, which feeds the device Writer) and, where src_idx is not NULL, src_idx[e] = the index in
+ * recs of kept record e, for gathering side arrays.  keys_cap / vals_cap are in BYTES, rec_cap in
+ * RECORDS (of key_end, val_end and src_idx alike).  *flags (device u32, cleared by the emit):
+ *    MTBLX_WHERE_OVERFLOW     a capacity is below what the totals ask for (keys: [1]; vals: [2];
+ *                             rec_cap: [0]);
+ *    MTBLX_WHERE_NOT_PLANNED  the workspace is not that of an mtblx_where_plan over this record count
+ *                             (the mark differs from every other workspace's);
+ *    MTBLX_WHERE_BADSEG       the plan met a bad seg_off.
+ * With any of them set NOTHING else is written: the outputs are as they were.
+ * The workspace (device, 256-byte aligned, mtblx_where_workspace_bytes; no fill needed; one call at a
+ * time) holds a header, 1 B per record and 32 B per tile of mtblx_where_tile() records: a workgroup
+ * owns a tile of consecutive records, so one segment of a million records costs what a million
+ * segments cost.  n < MTBLX_MERGE_MAX_RECORDS; n == 0 is legal.  Values are read at any alignment.
+ * MTBLX_E_INVAL before any device call: a bad mtblx_where, NULL recs, NULL or misaligned (256)
+ * workspace, ws_bytes too small, n too large, nseg above MTBLX_REDUCE_MAX_SEGMENTS, nseg != 0 with a
+ * NULL seg_off or seg_end, n != 0 with a NULL key_end or val_end (keys / vals may be NULL where every
+ * key / value is empty), key_end, val_end, seg_off, seg_end or seg_bad not 8-byte aligned; the plan:
+ * NULL totals; the emit: NULL out or flags (4-byte aligned), a NULL keys / vals with a non-zero
+ * capacity, a NULL key_end or val_end with a non-zero rec_cap, and key_end, val_end or src_idx not
+ * 8-byte aligned. */
+#define MTBLX_WHERE_ANY 1u        /* flags: at least one constrained field passes (default: all of them) */
+#define MTBLX_WHERE_VARINT 0x10u  /* flags: the fields are varints; the same bit as MTBLX_REDUCE_VARINT  */
+#define MTBLX_WHERE_OVERFLOW 1u
+#define MTBLX_WHERE_NOT_PLANNED 2u
+#define MTBLX_WHERE_BADSEG 8u
+typedef struct mtblx_where {
+  uint32_t nfields;   /* 1..MTBLX_REDUCE_MAX_FIELDS */
+  uint32_t flags;     /* MTBLX_WHERE_ANY | MTBLX_WHERE_VARINT */
+  uint8_t mask;       /* bit f: field f is constrained */
+  uint8_t outside;    /* bit f: field f must lie OUTSIDE [lo[f], hi[f]] (a subset of mask) */
+  uint64_t lo[8], hi[8];   /* inclusive, unsigned */
+} mtblx_where;
+typedef struct mtblx_filtered {
+  uint8_t* keys;       /* device: key of kept record e = keys[key_end[e-1] .. key_end[e])               */
+  uint64_t keys_cap;   /* bytes                                                                         */
+  uint8_t* vals;
+  uint64_t vals_cap;   /* bytes                                                                         */
+  uint64_t* key_end;   /* device [kept], u64 END offsets                                                */
+  uint64_t* val_end;
+  uint64_t* src_idx;   /* device [kept], may be NULL: the index in recs of every kept record            */
+  uint64_t rec_cap;    /* records: the capacity of key_end, val_end and src_idx                         */
+  uint32_t* flags;     /* device word, cleared by the call: MTBLX_WHERE_*                               */
+} mtblx_filtered;
+size_t mtblx_where_workspace_bytes(uint64_t nrec, uint32_t nseg);
+int mtblx_where_plan(const mtblx_records* recs, const mtblx_where* w, const uint64_t* seg_off, uint32_t nseg,
+                     uint64_t* totals, uint64_t* seg_end, uint64_t* seg_bad, void* workspace, size_t ws_bytes,
+                     void* stream);
+int mtblx_where_emit(const mtblx_records* recs, const mtblx_filtered* out, const void* workspace, size_t ws_bytes,
+                     void* stream);
+uint32_t mtblx_where_tile(void);         /* records per workgroup of the filter's kernels             */
+/* The fused aggregating walk: mtblx_scan_reduce (same arguments, same res[], same totals, same
+ * workspace, synchronous) with a predicate between the iterator and the fold.  Where the walk folds a
+ * record's value it first evaluates `where` on the same decoded fields -- lane f holds field f's
+ * bounds; one compare per lane and one ballot decide.  Per query: res[q].nrec, key_bytes, val_bytes
+ * and the status are exactly mtblx_scan_plan's (the predicate sits AFTER the iterator and after
+ * max_records); nbad[q] the bad values; nmatch[q] (device [nq], 8-byte aligned) the kept values;
+ * fields the ops over the kept values only, over nothing the identities.  Queries that are not
+ * MTBLX_SCAN_OK give zeros.  MTBLX_E_INVAL before any device call: everything mtblx_scan_reduce
+ * refuses, a bad mtblx_where, a layout of `where` (nfields and the varint bit) that is not the
+ * spec's, a NULL or misaligned nmatch. */
+int mtblx_scan_reduce_where(const uint8_t* file, uint64_t file_len, uint32_t version, int verify, uint64_t index_off,
+                            uint64_t index_len, const uint64_t* tab_start, const uint64_t* tab_doff,
+                            const uint64_t* tab_dlen, const int32_t* tab_st, uint32_t ntab, const uint8_t* dec,
+                            const int32_t* type, const uint8_t* keys, const uint64_t* key_end, const uint8_t* keys2,
+                            const uint64_t* key2_end, const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
+                            mtblx_scan_result* res, uint64_t* totals, void* workspace, size_t ws_bytes,
+                            const mtblx_reduce* spec, uint64_t* fields, uint64_t* nbad, const mtblx_where* where,
+                            uint64_t* nmatch, void* stream);
 
 /* ---- snappy raw decompression on the device (f4) ----
  * Reader::block's decompression step for CompressionType::Snappy (src/reader.rs:166-170 ->

@@ -428,7 +428,8 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
                                       const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
                                       const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
                                       mtblx_scan_result* res, uint64_t* totals, void* ws, const mtblx_reduce* spec,
-                                      uint64_t* fields, uint64_t* nbad, hipStream_t s);
+                                      uint64_t* fields, uint64_t* nbad, const mtblx_where* where, uint64_t* nmatch,
+                                      hipStream_t s);
 extern "C" int mtblx_reduce_seg_impl(const mtblx_records* recs, const uint64_t* seg_lo, const uint64_t* seg_hi,
                                      uint32_t nseg, const mtblx_reduce* spec, uint64_t* fields, uint64_t* nbad,
                                      uint32_t* flags, hipStream_t s);
@@ -451,7 +452,8 @@ extern "C" int mtblx_scan_reduce(const uint8_t* file, uint64_t file_len, uint32_
   if (nq == 0) return MTBLX_OK;
   return mtblx_scan_impl_reduce(file, file_len, version, verify, index_off, index_len, tab_start, tab_doff, tab_dlen,
                                 tab_st, ntab, dec, type, keys, key_end, keys2, key2_end, max_records, max_blocks, nq,
-                                res, totals, ws, spec, fields, nbad, reinterpret_cast<hipStream_t>(stream));
+                                res, totals, ws, spec, fields, nbad, nullptr, nullptr,
+                                reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int mtblx_reduce_segments(const mtblx_records* recs, const uint64_t* seg_lo, const uint64_t* seg_hi,
@@ -544,6 +546,97 @@ extern "C" int mtblx_reduce_encode(const uint64_t* fields, uint64_t n, const mtb
   if (cap < (varint ? 10ull : 8ull) * spec->nfields * n || wsb < mtblx_reduce_encode_impl_ws_bytes(n))
     return MTBLX_E_INVAL;
   return mtblx_reduce_encode_impl(fields, n, spec, vals, val_end, cap, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- value predicates (csrc/where.hip): every argument is checked before any HIP call ----
+extern "C" size_t mtblx_where_impl_ws_bytes(uint64_t n);
+extern "C" int mtblx_where_impl_plan(const mtblx_records* recs, const mtblx_where* where, const uint64_t* seg_off,
+                                     uint32_t nseg, uint64_t* totals, uint64_t* seg_end, uint64_t* seg_bad, void* ws,
+                                     hipStream_t s);
+extern "C" int mtblx_where_impl_emit(const mtblx_records* recs, const mtblx_filtered* out, const void* ws,
+                                     hipStream_t s);
+
+extern "C" size_t mtblx_where_workspace_bytes(uint64_t nrec, uint32_t nseg) {
+  (void)nseg;   // the segments are read where the caller keeps them
+  return mtblx_where_impl_ws_bytes(nrec);
+}
+
+static int where_spec_check(const mtblx_where* w) {
+  if (!w || w->nfields < 1 || w->nfields > MTBLX_REDUCE_MAX_FIELDS) return MTBLX_E_INVAL;
+  if (w->flags & ~(MTBLX_WHERE_ANY | MTBLX_WHERE_VARINT)) return MTBLX_E_INVAL;
+  const uint32_t all = (1u << w->nfields) - 1u;
+  if ((w->mask & ~all) || (w->outside & ~all) || (w->outside & ~w->mask)) return MTBLX_E_INVAL;
+  return MTBLX_OK;
+}
+
+// what mtblx_where_plan and mtblx_where_emit check alike
+static int where_check(const mtblx_records* recs, const void* ws, size_t wsb) {
+  if (!recs || recs->n >= MTBLX_MERGE_MAX_RECORDS) return MTBLX_E_INVAL;
+  if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255u) != 0 || wsb < mtblx_where_impl_ws_bytes(recs->n))
+    return MTBLX_E_INVAL;
+  if (recs->n && (!recs->key_end || !recs->val_end)) return MTBLX_E_INVAL;   // keys / vals may be NULL
+  if ((reinterpret_cast<uintptr_t>(recs->key_end) | reinterpret_cast<uintptr_t>(recs->val_end)) & 7u)
+    return MTBLX_E_INVAL;
+  return MTBLX_OK;
+}
+
+extern "C" int mtblx_where_plan(const mtblx_records* recs, const mtblx_where* where, const uint64_t* seg_off,
+                                uint32_t nseg, uint64_t* totals, uint64_t* seg_end, uint64_t* seg_bad, void* ws,
+                                size_t wsb, void* stream) {
+  if (!totals) return MTBLX_E_INVAL;
+  int c = where_spec_check(where);
+  if (c != MTBLX_OK) return c;
+  c = where_check(recs, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  if (nseg > MTBLX_REDUCE_MAX_SEGMENTS || (nseg && (!seg_off || !seg_end))) return MTBLX_E_INVAL;
+  if ((reinterpret_cast<uintptr_t>(seg_off) | reinterpret_cast<uintptr_t>(seg_end) |
+       reinterpret_cast<uintptr_t>(seg_bad)) & 7u)
+    return MTBLX_E_INVAL;
+  return mtblx_where_impl_plan(recs, where, seg_off, nseg, totals, seg_end, seg_bad, ws,
+                               reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mtblx_where_emit(const mtblx_records* recs, const mtblx_filtered* out, const void* ws, size_t wsb,
+                                void* stream) {
+  if (!out || !out->flags || (reinterpret_cast<uintptr_t>(out->flags) & 3u)) return MTBLX_E_INVAL;
+  if ((!out->keys && out->keys_cap) || (!out->vals && out->vals_cap) ||
+      ((!out->key_end || !out->val_end) && out->rec_cap))
+    return MTBLX_E_INVAL;
+  if ((reinterpret_cast<uintptr_t>(out->key_end) | reinterpret_cast<uintptr_t>(out->val_end) |
+       reinterpret_cast<uintptr_t>(out->src_idx)) & 7u)
+    return MTBLX_E_INVAL;
+  const int c = where_check(recs, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  return mtblx_where_impl_emit(recs, out, ws, reinterpret_cast<hipStream_t>(stream));
+}
+
+// the fused aggregating walk: mtblx_scan_reduce's checks, then the predicate's and its layout against the spec's
+extern "C" int mtblx_scan_reduce_where(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
+                                       uint64_t index_off, uint64_t index_len, const uint64_t* tab_start,
+                                       const uint64_t* tab_doff, const uint64_t* tab_dlen, const int32_t* tab_st,
+                                       uint32_t ntab, const uint8_t* dec, const int32_t* type, const uint8_t* keys,
+                                       const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
+                                       const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
+                                       mtblx_scan_result* res, uint64_t* totals, void* ws, size_t wsb,
+                                       const mtblx_reduce* spec, uint64_t* fields, uint64_t* nbad,
+                                       const mtblx_where* where, uint64_t* nmatch, void* stream) {
+  if (!fields || !nbad || !nmatch ||
+      ((reinterpret_cast<uintptr_t>(fields) | reinterpret_cast<uintptr_t>(nbad) | reinterpret_cast<uintptr_t>(nmatch)) & 7u))
+    return MTBLX_E_INVAL;
+  int c = spec_check(spec);
+  if (c != MTBLX_OK) return c;
+  c = where_spec_check(where);
+  if (c != MTBLX_OK) return c;
+  const bool sv = spec->op[0] & MTBLX_REDUCE_VARINT, wv = where->flags & MTBLX_WHERE_VARINT;
+  if (where->nfields != spec->nfields || sv != wv) return MTBLX_E_INVAL;
+  c = scan_plan_check(file, version, tab_start, tab_doff, tab_dlen, tab_st, ntab, dec, type, keys, key_end, keys2,
+                      key2_end, nq, res, totals, ws, wsb);
+  if (c != MTBLX_OK) return c;
+  if (nq == 0) return MTBLX_OK;
+  return mtblx_scan_impl_reduce(file, file_len, version, verify, index_off, index_len, tab_start, tab_doff, tab_dlen,
+                                tab_st, ntab, dec, type, keys, key_end, keys2, key2_end, max_records, max_blocks, nq,
+                                res, totals, ws, spec, fields, nbad, where, nmatch,
+                                reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- bounds-checked diagnostic build only (csrc/bounds.h, Makefile target `bounds`) ----

@@ -124,16 +124,46 @@ struct RAcc<true> {
 };
 struct RedV : Red {};   // the same with varint-coded values: the encoding is the kernel's template argument
 __device__ __forceinline__ const Red& red_of(const Red& r) { return r; }
+
+// the predicate of the fused walk (mtblx_scan_reduce_where): a further trailing argument after the
+// Red / RedV.  Lane f < nf keeps field f's bounds beside its accumulator
+struct Whr {
+  uint64_t lo[MTBLX_REDUCE_MAX_FIELDS], hi[MTBLX_REDUCE_MAX_FIELDS];
+  uint32_t mask, outside, any;
+  uint64_t* nmatch;   // [nq]
+};
+__device__ __forceinline__ const Red& red_of(const Red& r, const Whr&) { return r; }
+__device__ __forceinline__ const Whr& whr_of(const Red&, const Whr& w) { return w; }
+struct WAcc : RAcc<true> {   // what a lane of the fused walk carries: RAcc<true>, and
+  uint64_t lo = 0, hi = 0, match = 0;
+  bool on = false, outside = false;   // this lane's field is constrained; must lie outside [lo, hi]
+};
+template <bool RED, bool WHR>
+struct AccOf { typedef RAcc<RED> type; };
+template <>
+struct AccOf<true, true> { typedef WAcc type; };
+// one compare per lane and one ballot: the bits of the constrained fields that pass, against the mask
+__device__ __forceinline__ bool whr_keeps(const WAcc& wa, const Whr& wh, uint64_t x) {
+  const bool in = wa.lo <= x && x <= wa.hi;
+  const uint32_t pass = (uint32_t)__ballot(wa.on && in != wa.outside);
+  return wh.any ? pass != 0 : pass == wh.mask;
+}
+
 template <class... RD>
 struct IsVarint { static constexpr bool value = false; };
 template <>
 struct IsVarint<RedV> { static constexpr bool value = true; };
+template <>
+struct IsVarint<RedV, Whr> { static constexpr bool value = true; };
 
 // The plan walk, a kernel template on its trailing arguments.  k_scan_plan<> is the plan as it
 // always was, with the same kernel arguments.  k_scan_plan<Red> (mtblx_scan_reduce) also folds every
 // accepted record whose value is 8 * nf bytes long into the lanes' accumulators where the walk
 // counts it, and counts the others in nbad.  k_scan_plan<RedV> does so for the values that are nf
-// varints back to back (reduce_ops.h, r_load_varint_lane).
+// varints back to back (reduce_ops.h, r_load_varint_lane).  k_scan_plan<Red, Whr> and
+// k_scan_plan<RedV, Whr> (mtblx_scan_reduce_where) evaluate the predicate on the fields a record's
+// value was just decoded to, fold the kept values alone and count them in nmatch; the counts of the
+// plan, the stop rules and max_records do not see the predicate.
 template <class... RD>
 __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
                                                    uint64_t idx_off, uint64_t idx_len, DecTab tab, const int32_t* type,
@@ -141,6 +171,7 @@ __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t
                                                    const uint64_t* qend2, const uint64_t* maxrec, uint32_t max_blocks,
                                                    uint32_t nq, mtblx_scan_result* wres, Land* land, RD... red) {
   constexpr bool RED = sizeof...(RD) != 0;
+  constexpr bool WHR = sizeof...(RD) == 2;
   __shared__ uint32_t T[256];
   for (int i = threadIdx.x; i < 256; i += blockDim.x) T[i] = mtblx_crc::kTab.byte[i];
   __syncthreads();
@@ -167,10 +198,21 @@ __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t
     Land ld{};
     Blk ib{}, db{};
     It ii{}, di{}, dj{};
-    RAcc<RED> ra;
+    typename AccOf<RED, WHR>::type ra;
     if constexpr (RED) {
       ra.op = r_op(red_of(red...).sp, lane & 7);
       ra.acc = r_ident(ra.op);
+    }
+    if constexpr (WHR) {
+      const Whr& wh = whr_of(red...);
+#pragma unroll
+      for (int f = 0; f < MTBLX_REDUCE_MAX_FIELDS; ++f)
+        if ((lane & 7) == f) {
+          ra.lo = wh.lo[f];
+          ra.hi = wh.hi[f];
+        }
+      ra.on = lane < MTBLX_REDUCE_MAX_FIELDS && ((wh.mask >> lane) & 1u);
+      ra.outside = lane < MTBLX_REDUCE_MAX_FIELDS && ((wh.outside >> lane) & 1u);
     }
     do {
       if (block_init(file + idx_off, idx_len, ib) != 0) break;   // the Reader's index block
@@ -233,7 +275,27 @@ __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t
         vb += di.vlen;
         if constexpr (RED) {   // the value is db.d + [voff, voff + vlen), inside the block (checked above)
           const Red& rd = red_of(red...);
-          if constexpr (IsVarint<RD...>::value) {
+          if constexpr (WHR) {   // the mask names fields below nf only: lanes at or above nf never vote
+            const Whr& wh = whr_of(red...);
+            uint64_t x = 0;
+            bool ok;
+            if constexpr (IsVarint<RD...>::value) {
+              ok = r_load_varint_lane<true>(db.d + di.voff, di.vlen, rd.nf, (uint32_t)lane, &x);
+            } else {
+              ok = di.vlen == 8ull * rd.nf;
+              if (ok && (uint32_t)lane < rd.nf) {
+                const uint8_t* vp = db.d + di.voff + 8u * (uint32_t)lane;   // any alignment
+                MTBLX_CHK(vp, 8);
+                x = *reinterpret_cast<const u64u*>(vp);
+              }
+            }
+            if (!ok) {
+              ++ra.bad;
+            } else if (whr_keeps(ra, wh, x)) {
+              ++ra.match;
+              if ((uint32_t)lane < rd.nf) ra.acc = r_apply(ra.op, ra.acc, x);
+            }
+          } else if constexpr (IsVarint<RD...>::value) {
             uint64_t x = 0;
             if (!r_load_varint_lane<true>(db.d + di.voff, di.vlen, rd.nf, (uint32_t)lane, &x)) ++ra.bad;
             else if ((uint32_t)lane < rd.nf) ra.acc = r_apply(ra.op, ra.acc, x);
@@ -269,6 +331,11 @@ __global__ void __launch_bounds__(256) k_scan_plan(const uint8_t* file, uint64_t
       }
       MTBLX_CHK(rd.nbad + q, 8);
       if (lane == 0) rd.nbad[q] = ok ? ra.bad : 0;
+      if constexpr (WHR) {
+        const Whr& wh = whr_of(red...);
+        MTBLX_CHK(wh.nmatch + q, 8);
+        if (lane == 0) wh.nmatch[q] = ok ? ra.match : 0;
+      }
     }
   }
 }
@@ -470,7 +537,8 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
                                       const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
                                       const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
                                       mtblx_scan_result* res, uint64_t* totals, void* ws, const mtblx_reduce* spec,
-                                      uint64_t* fields, uint64_t* nbad, hipStream_t s);
+                                      uint64_t* fields, uint64_t* nbad, const mtblx_where* where, uint64_t* nmatch,
+                                      hipStream_t s);
 
 // arguments already checked (mtblx_api.cpp): ws 256-byte aligned and large enough, every type in 0..3
 extern "C" int mtblx_scan_impl_plan(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
@@ -481,11 +549,12 @@ extern "C" int mtblx_scan_impl_plan(const uint8_t* file, uint64_t file_len, uint
                                     uint32_t nq, mtblx_scan_result* res, uint64_t* totals, void* ws, hipStream_t s) {
   return mtblx_scan_impl_reduce(file, file_len, version, verify, index_off, index_len, tab_start, tab_doff, tab_dlen,
                                 tab_st, ntab_in, dec, type, keys, key_end, keys2, key2_end, max_records, max_blocks, nq,
-                                res, totals, ws, nullptr, nullptr, nullptr, s);
+                                res, totals, ws, nullptr, nullptr, nullptr, nullptr, nullptr, s);
 }
 
 // spec == NULL: the plan alone.  Else k_scan_plan<Red> (k_scan_plan<RedV> for a varint spec) takes
-// k_scan_plan<>'s place and fills fields / nbad.
+// k_scan_plan<>'s place and fills fields / nbad; with `where` (its layout is the spec's: checked by
+// mtblx_api.cpp) k_scan_plan<Red, Whr> / k_scan_plan<RedV, Whr> do and fill nmatch too.
 extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, uint32_t version, int verify,
                                       uint64_t index_off, uint64_t index_len, const uint64_t* tab_start,
                                       const uint64_t* tab_doff, const uint64_t* tab_dlen, const int32_t* tab_st,
@@ -493,7 +562,8 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
                                       const uint64_t* key_end, const uint8_t* keys2, const uint64_t* key2_end,
                                       const uint64_t* max_records, uint32_t max_blocks, uint32_t nq,
                                       mtblx_scan_result* res, uint64_t* totals, void* ws, const mtblx_reduce* spec,
-                                      uint64_t* fields, uint64_t* nbad, hipStream_t s) {
+                                      uint64_t* fields, uint64_t* nbad, const mtblx_where* where, uint64_t* nmatch,
+                                      hipStream_t s) {
   using namespace mtblx_rd;
   RedV rd{};
   bool varint = false;
@@ -502,6 +572,18 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
     rd.nf = spec->nfields;
     rd.fields = fields;
     rd.nbad = nbad;
+  }
+  Whr wh{};
+  if (where) {
+    if (!spec) return MTBLX_E_INVAL;
+    for (uint32_t f = 0; f < MTBLX_REDUCE_MAX_FIELDS; ++f) {
+      wh.lo[f] = where->lo[f];
+      wh.hi[f] = where->hi[f];
+    }
+    wh.mask = where->mask;
+    wh.outside = where->outside;
+    wh.any = where->flags & MTBLX_WHERE_ANY;
+    wh.nmatch = nmatch;
   }
   const DecTab tab = dec ? DecTab{tab_start, tab_doff, tab_dlen, tab_st, ntab_in, dec}
                          : DecTab{nullptr, nullptr, nullptr, nullptr, 0u, nullptr};
@@ -516,7 +598,25 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
   const uint64_t need = ((uint64_t)nq + 3u) / 4u, cap = (uint64_t)mtblx_dev::cu_count() * 8u;
   const uint64_t ntab = tab.dec ? tab.n : 0;
   (void)ntab;   // read by the bounds-checked build only
-  if (!spec)
+  if (where && varint)
+    MTBLX_LAUNCH((MTBLX_R(file, file_len), MTBLX_R(tab.start, 8ull * ntab), MTBLX_R(tab.doff, 8ull * ntab),
+                  MTBLX_R(tab.dlen, 8ull * ntab), MTBLX_R(tab.st, 4ull * ntab), tab.dec, keys,
+                  MTBLX_R(key_end, 8ull * nq), keys2, MTBLX_R(key2_end, 8ull * nq), MTBLX_R(max_records, 8ull * nq),
+                  MTBLX_R(w, L.total), MTBLX_R(fields, 8ull * nq * rd.nf), MTBLX_R(nbad, 8ull * nq),
+                  MTBLX_R(nmatch, 8ull * nq)),
+                 (k_scan_plan<RedV, Whr>), dim3((unsigned)(need < cap ? need : cap)), dim3(256), 0, s, file, file_len,
+                 version, verify, index_off, index_len, tab, dtype, keys, key_end, keys2, key2_end, max_records,
+                 max_blocks, nq, wres, land, rd, wh);
+  else if (where)
+    MTBLX_LAUNCH((MTBLX_R(file, file_len), MTBLX_R(tab.start, 8ull * ntab), MTBLX_R(tab.doff, 8ull * ntab),
+                  MTBLX_R(tab.dlen, 8ull * ntab), MTBLX_R(tab.st, 4ull * ntab), tab.dec, keys,
+                  MTBLX_R(key_end, 8ull * nq), keys2, MTBLX_R(key2_end, 8ull * nq), MTBLX_R(max_records, 8ull * nq),
+                  MTBLX_R(w, L.total), MTBLX_R(fields, 8ull * nq * rd.nf), MTBLX_R(nbad, 8ull * nq),
+                  MTBLX_R(nmatch, 8ull * nq)),
+                 (k_scan_plan<Red, Whr>), dim3((unsigned)(need < cap ? need : cap)), dim3(256), 0, s, file, file_len,
+                 version, verify, index_off, index_len, tab, dtype, keys, key_end, keys2, key2_end, max_records,
+                 max_blocks, nq, wres, land, static_cast<const Red&>(rd), wh);
+  else if (!spec)
     MTBLX_LAUNCH((MTBLX_R(file, file_len), MTBLX_R(tab.start, 8ull * ntab), MTBLX_R(tab.doff, 8ull * ntab),
                   MTBLX_R(tab.dlen, 8ull * ntab), MTBLX_R(tab.st, 4ull * ntab), tab.dec, keys,
                   MTBLX_R(key_end, 8ull * nq), keys2, MTBLX_R(key2_end, 8ull * nq), MTBLX_R(max_records, 8ull * nq),

@@ -13,12 +13,16 @@ Package layout
               (csrc/merge_dev.h k_group_select)
   rollup.py   GroupBy / rollup_records / Rollup: records grouped by a key prefix, one aggregate per group
               (csrc/rollup.hip); Reader.rollup / rollup_batch and Merger.rollup / rollup_batch sit on it
+  where.py    Where / filter_records / Filtered / filter_file: records kept or dropped by the fields of their
+              value (csrc/where.hip)
 """
 from ._lib import EXPORTS, LIB_PATH, lib  # noqa: F401
 from .reduce import MergeError, Reduce, ReduceBatch, reduce_segments  # noqa: F401
 from .rollup import GroupBy, Rollup, reduce_encode, rollup_records  # noqa: F401
 from . import setops  # noqa: F401
 from .setops import Select  # noqa: F401
+from . import where  # noqa: F401
+from .where import Filtered, Where, filter_records  # noqa: F401
 from .writer import CompressionType, OutOfOrderKey, Writer, WriterBuilder  # noqa: F401
 
 
@@ -34,4 +38,5 @@ def __getattr__(name):   # Merger / MergerBuilder / Sorter / SorterBuilder need 
 
 __all__ = ["Writer", "WriterBuilder", "CompressionType", "OutOfOrderKey", "Merger", "MergerBuilder", "Sorter", "SorterBuilder",
            "MergedScanBatch", "merge_segments", "Select", "setops",
-           "Reduce", "MergeError", "GroupBy", "Rollup", "rollup_records", "reduce_encode", "lib", "LIB_PATH", "EXPORTS"]
+           "Reduce", "MergeError", "GroupBy", "Rollup", "rollup_records", "reduce_encode",
+           "Where", "Filtered", "filter_records", "where", "lib", "LIB_PATH", "EXPORTS"]

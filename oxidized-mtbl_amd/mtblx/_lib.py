@@ -54,6 +54,8 @@ EXPORTS = [
     "mtblx_scan_reduce", "mtblx_reduce_segments", "mtblx_reduce_seg_tile",
     "mtblx_rollup_workspace_bytes", "mtblx_rollup_plan", "mtblx_rollup_emit", "mtblx_rollup_tile",
     "mtblx_reduce_encode_workspace_bytes", "mtblx_reduce_encode",
+    "mtblx_where_workspace_bytes", "mtblx_where_plan", "mtblx_where_emit", "mtblx_where_tile",
+    "mtblx_scan_reduce_where",
     "mtblx_stage_workspace_bytes", "mtblx_stage_plan", "mtblx_stage_emit", "mtblx_scan_touch", "mtblx_bitmap_compact",
     "mtblx_table_gather", "mtblx_dir_ascends",
 ]
@@ -72,6 +74,8 @@ REDUCE_MAX_SEGMENTS = 0xFFFFFF00               # MTBLX_REDUCE_MAX_SEGMENTS: nseg
 REDUCE_SEG_TILE = 1024                         # MTBLX_REDUCE_SEG_TILE: records per workgroup of mtblx_reduce_segments
 GROUP_LENGTH, GROUP_DELIM = 0, 1                # mtblx_group.kind
 ROLLUP_OVERFLOW, ROLLUP_NOT_PLANNED, ROLLUP_BADSEG = 1, 2, 8   # *flags of mtblx_rollup_emit
+WHERE_ANY, WHERE_VARINT = 1, 0x10                # mtblx_where.flags
+WHERE_OVERFLOW, WHERE_NOT_PLANNED, WHERE_BADSEG = 1, 2, 8      # *flags of mtblx_where_emit; BADSEG also totals[5]
 SORT_TILE = 1024                               # MTBLX_SORT_TILE: handles per tile-sorted run of mtblx_sort_plan
 PLAN_OUT_OF_ORDER, PLAN_PANIC, PLAN_TOO_LONG = 1, 2, 4
 SCAN_OK, SCAN_LARGE, SCAN_FALLBACK = range(3)  # mtblx_scan_result.status
@@ -120,6 +124,17 @@ class Rolled(C.Structure):   # mtblx_rolled (capacities in bytes)
     _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("key_end", C.c_void_p), ("key_end_cap", C.c_uint64),
                 ("grp_rec", C.c_void_p), ("grp_rec_cap", C.c_uint64), ("seg_grp", C.c_void_p),
                 ("seg_grp_cap", C.c_uint64), ("flags", C.c_void_p)]
+
+
+class WhereSpec(C.Structure):   # mtblx_where
+    _fields_ = [("nfields", C.c_uint32), ("flags", C.c_uint32), ("mask", C.c_uint8), ("outside", C.c_uint8),
+                ("lo", C.c_uint64 * 8), ("hi", C.c_uint64 * 8)]
+
+
+class Filtered(C.Structure):   # mtblx_filtered (keys_cap / vals_cap in bytes, rec_cap in records)
+    _fields_ = [("keys", C.c_void_p), ("keys_cap", C.c_uint64), ("vals", C.c_void_p), ("vals_cap", C.c_uint64),
+                ("key_end", C.c_void_p), ("val_end", C.c_void_p), ("src_idx", C.c_void_p), ("rec_cap", C.c_uint64),
+                ("flags", C.c_void_p)]
 
 
 class ScanResult(C.Structure):   # mtblx_scan_result
@@ -394,6 +409,17 @@ def lib() -> C.CDLL:
         L.mtblx_reduce_encode.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ReduceSpec), C.c_void_p, C.c_void_p,
                                           C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p]
         L.mtblx_reduce_encode.restype = C.c_int
+        L.mtblx_where_workspace_bytes.argtypes = [C.c_uint64, C.c_uint32]
+        L.mtblx_where_workspace_bytes.restype = C.c_size_t
+        L.mtblx_where_plan.argtypes = [C.POINTER(Records), C.POINTER(WhereSpec), C.c_void_p, C.c_uint32, u64p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_where_plan.restype = C.c_int
+        L.mtblx_where_emit.argtypes = [C.POINTER(Records), C.POINTER(Filtered), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mtblx_where_emit.restype = C.c_int
+        L.mtblx_where_tile.restype = C.c_uint32
+        L.mtblx_scan_reduce_where.argtypes = L.mtblx_scan_reduce.argtypes[:-1] + [C.POINTER(WhereSpec), C.c_void_p,
+                                                                                  C.c_void_p]
+        L.mtblx_scan_reduce_where.restype = C.c_int
         L.mtblx_scan_emit.argtypes = _file + [C.c_uint64, C.c_uint64] + _tab + [
             C.c_uint32, C.POINTER(Scanned), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mtblx_scan_emit.restype = C.c_int

@@ -591,19 +591,25 @@ class Merger:
             return iter(self._merged_list())
         return iter(_records_list(self.records()))
 
-    def records(self) -> DeviceRecords:
-        """the merged stream on the device (what encode.write_file takes)"""
+    def records(self, where=None) -> DeviceRecords:
+        """the merged stream on the device (what encode.write_file takes).  where (a where.Where): only
+        the records whose MERGED value it keeps -- the predicate sees the value after the merge function,
+        the empty-key quirk and any Select (filter_records over the merged records)"""
+        from .where import as_where, filter_records
+        where = as_where(where)                             # refused before any device work
+        s = self._s()
         if callable(self.merge):
-            s = self._s()
-            return DeviceRecords.from_list(self._merged_list(), device=self._device() or "cuda", stream=s)
-        return self._run(self.merge)
+            r = DeviceRecords.from_list(self._merged_list(), device=self._device() or "cuda", stream=s)
+        else:
+            r = self._run(self.merge)
+        return r if where is None else filter_records(r, where, None, s).records
 
     def write_file(self, block_size: int = 8192, restart_interval: int = 16,
-                   compression: int = CompressionType.None_) -> torch.Tensor:
-        """the merged .mtbl file (device uint8), written by the device Writer"""
+                   compression: int = CompressionType.None_, where=None) -> torch.Tensor:
+        """the merged .mtbl file (device uint8), written by the device Writer; where: as records(where=)"""
         s = self._s()
         with torch.cuda.stream(s):   # records() and the Writer on one stream, also when self.stream is None
-            return encode.write_file(self.records(), block_size, restart_interval, stream=s, compression=compression)
+            return encode.write_file(self.records(where), block_size, restart_interval, stream=s, compression=compression)
 
     def write_into(self, writer) -> None:
         """Merger::write_into (src/merger.rs:149-156) for the host Writer"""

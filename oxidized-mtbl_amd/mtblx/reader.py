@@ -895,10 +895,11 @@ class Reader:
         return iterator.bulk(self, "range", bytes(start), bytes(end))
 
     # ------------------------------------------------------------------ batched scans
-    def _scan_plan(self, queries, max_blocks, max_records, stream, reduce=None):
+    def _scan_plan(self, queries, max_blocks, max_records, stream, reduce=None, where=None):
         """mtblx_scan_plan over `queries` -> (res uint8 [nq * 64] device, totals, workspace, per-query
         limits, table arguments).  With a Reduce the call is mtblx_scan_reduce and the tuple ends with
-        (fields int64 [nq, F], nbad int64 [nq])."""
+        (fields int64 [nq, F], nbad int64 [nq]); with a Where too it is mtblx_scan_reduce_where and the
+        last tuple is (fields, nbad, nmatch int64 [nq])."""
         from . import iterator
         dev = self.file.device
         nq = len(queries)
@@ -963,6 +964,15 @@ class Reader:
         spec = reduce.cstruct()
         fields = torch.zeros((max(nq, 1), len(reduce.ops)), dtype=torch.int64, device=dev)
         nbad = torch.zeros(max(nq, 1), dtype=torch.int64, device=dev)
+        if where is not None:
+            wspec = where.cstruct()
+            nmatch = torch.zeros(max(nq, 1), dtype=torch.int64, device=dev)
+            rc = L.mtblx_scan_reduce_where(*args, C.byref(spec), C.c_void_p(fields.data_ptr()),
+                                           C.c_void_p(nbad.data_ptr()), C.byref(wspec), C.c_void_p(nmatch.data_ptr()),
+                                           C.c_void_p(codec._stream_handle(stream)))
+            if rc != 0:
+                raise RuntimeError(f"mtblx_scan_reduce_where failed: {rc}")
+            return res, [int(x) for x in totals], ws, wsb, limits, tab, keep, (fields[:nq], nbad[:nq], nmatch[:nq])
         rc = L.mtblx_scan_reduce(*args, C.byref(spec), C.c_void_p(fields.data_ptr()), C.c_void_p(nbad.data_ptr()),
                                  C.c_void_p(codec._stream_handle(stream)))
         if rc != 0:
@@ -979,7 +989,7 @@ class Reader:
         w = res.view(torch.int64).view(-1, 8)[:nq]
         return res.view(torch.int32).view(-1, 16)[:nq, 0], w[:, 1], w[:, 2], w[:, 3]
 
-    def scan_batch(self, queries, max_blocks: int = 64, max_records=None, stream=None) -> "ScanBatch":
+    def scan_batch(self, queries, max_blocks: int = 64, max_records=None, stream=None, where=None) -> "ScanBatch":
         """iter_from / get / iter_prefix / iter_range for a batch of queries: one plan, one allocation
         sized from its totals, one emit (mtblx_scan_plan / mtblx_scan_emit).  `queries`: ("from", k),
         ("get", k), ("prefix", p) or ("range", a, b); `max_records`: None, one limit, or one per query
@@ -988,10 +998,43 @@ class Reader:
         iterator.bulk() with the limit applied; so is every query when the index block is not
         regular.  ("get", k) is Reader::get: at most one record.  Everything -- the uploads, the
         on-demand staging, plan and emit, the read-backs and the seek-path answers -- runs on
-        `stream` (default: the current stream), which the call synchronises."""
+        `stream` (default: the current stream), which the call synchronises.  where (a where.Where):
+        the ScanBatch then reports, per query, the records whose value it keeps -- emit plus
+        filter_records over the emitted buffers with the queries as segments, before anything is read
+        back; `max_records` cuts before the filter; the bad values it dropped are `nbad` (int64 [nq])."""
+        from .where import as_where
+        where = as_where(where)
         stream = self._s(stream)
         with torch.cuda.stream(stream):
-            return self._scan_batch(list(queries), max_blocks, max_records, stream)
+            sb = self._scan_batch(list(queries), max_blocks, max_records, stream)
+            return sb if where is None else self._filter_scan(sb, where, stream)
+
+    def _filter_scan(self, sb: "ScanBatch", where, stream) -> "ScanBatch":
+        """`sb` with every query's records filtered on the device: the kernel path's buffers in one
+        filter_records whose segments are the queries, a seek-path answer from its own device records"""
+        from .encode import DeviceRecords
+        from .where import filter_records
+        f = filter_records(DeviceRecords(sb.keys, sb.key_end, sb.vals, sb.val_end), where, sb.rec_off, stream)
+        r, nq = f.records, sb.nq
+        rec_off = f.seg_off()
+        kb = torch.cat([r.key_end.new_zeros(1), r.key_end])[rec_off]   # the bytes before every query's kept records
+        vb = torch.cat([r.val_end.new_zeros(1), r.val_end])[rec_off]
+        host = sb._res.copy()
+        ro, kh, vh = (t.cpu().numpy() for t in (rec_off, kb, vb))       # three words per query, on `stream`
+        host["nrec"], host["rec_base"] = np.diff(ro), ro[:-1]
+        host["key_bytes"], host["key_base"] = np.diff(kh), kh[:-1]
+        host["val_bytes"], host["val_base"] = np.diff(vh), vh[:-1]
+        nbad = f.seg_bad.clone()
+        served = {}
+        for q, sc in sb._served.items():
+            n = sc.nrec
+            g = filter_records(DeviceRecords(sc.keys, sc.key_end[:n], sc.vals, sc.val_end[:n]), where, None, stream)
+            served[q] = Scan(sc.end, sc.err, g.nkept, g.records.keys, g.records.vals, g.records.key_end,
+                             g.records.val_end, stream)
+            nbad[q] = g.nbad
+        out = ScanBatch(nq, r.keys, r.vals, r.key_end, r.val_end, rec_off, sb.status, host, served, stream)
+        out.nbad = nbad
+        return out
 
     def _scan_limited(self, query, m, stream) -> Scan:
         """one query of a batch through the seek path (iterator.bulk), cut at its limit `m`"""
@@ -1053,7 +1096,8 @@ class Reader:
         served = {int(q): limited(int(q), limits[int(q)]) for q in np.nonzero(host["status"] != _lib.SCAN_OK)[0]}
         return ScanBatch(nq, keys, vals, key_end, val_end, rec_off, status, host, served, stream)
 
-    def reduce_batch(self, queries, reduce, max_blocks: int = 64, max_records=None, stream=None) -> "ReduceBatch":
+    def reduce_batch(self, queries, reduce, max_blocks: int = 64, max_records=None, stream=None,
+                     where=None) -> "ReduceBatch":
         """scan_batch that aggregates instead of returning records: per query, `reduce` (a Reduce or a
         shorthand name) folded over the values of the records scan_batch would report (same stop rules,
         same `max_records`, ("get", k) at most one record), as Reduce.fold defines it.  One
@@ -1062,16 +1106,24 @@ class Reader:
         hands back (SCAN_LARGE, SCAN_FALLBACK) and every query of a reader with an irregular index is
         answered by iterator.bulk() with the limit applied and its device records are reduced by
         reduce_segments: no record is copied to the host.  Everything runs on `stream` (default: the
-        current stream), which the call synchronises."""
+        current stream), which the call synchronises.  where (a where.Where of the Reduce's layout,
+        else ValueError): the fused walk mtblx_scan_reduce_where -- `nrec` and the status stay what
+        scan_batch reports (the predicate sits after the iterator and after `max_records`), `nbad`
+        counts the bad values, `nmatch` the kept ones, and `fields` folds the kept values alone; a
+        handed-back query goes through filter_records, then reduce_segments."""
         from .reduce import as_reduce
+        from .where import as_where
         red = as_reduce(reduce)
         if red is None:
             raise ValueError(f"reduce_batch: {reduce!r} is not a Reduce")
+        where = as_where(where)
+        if where is not None and not where.same_layout(red):
+            raise ValueError(f"reduce_batch: {where!r} has not the layout of {red!r}")
         stream = self._s(stream)
         with torch.cuda.stream(stream):
-            return self._reduce_batch(list(queries), red, max_blocks, max_records, stream)
+            return self._reduce_batch(list(queries), red, max_blocks, max_records, stream, where)
 
-    def _reduce_batch(self, queries, red, max_blocks, max_records, stream) -> "ReduceBatch":
+    def _reduce_batch(self, queries, red, max_blocks, max_records, stream, where=None) -> "ReduceBatch":
         from .encode import DeviceRecords
         from .reduce import ReduceBatch, _signed, reduce_segments
         dev = self.file.device
@@ -1083,9 +1135,11 @@ class Reader:
             nbad = torch.zeros(nq, dtype=torch.int64, device=dev)
             nrec = torch.zeros(nq, dtype=torch.int64, device=dev)
             status = torch.full((nq,), _lib.SCAN_FALLBACK, dtype=torch.int32, device=dev)
+            nmatch = torch.zeros(nq, dtype=torch.int64, device=dev) if where is not None else None
             back, n_large, n_fallback = range(nq), 0, nq
         else:
-            res, _, _, _, limits, _, _, (fields, nbad) = self._scan_plan(queries, max_blocks, max_records, stream, red)
+            res, _, _, _, limits, _, _, outs = self._scan_plan(queries, max_blocks, max_records, stream, red, where)
+            fields, nbad, nmatch = outs if where is not None else (*outs, None)
             # the one read-back: mtblx_scan_reduce has synchronised `stream`
             host = np.frombuffer(res.cpu().numpy().tobytes(), np.dtype(_lib.ScanResult))[:nq]
             nrec = res.view(torch.int64).view(-1, 8)[:nq, 1].clone()
@@ -1097,48 +1151,61 @@ class Reader:
         for q in back:   # the seek path's answer stays on the device: one segment over its records
             sc = self._scan_limited(queries[q], limits[q], stream)
             n = sc.nrec
-            f, nb = reduce_segments(DeviceRecords(sc.keys, sc.key_end[:n], sc.vals, sc.val_end[:n]), [0], [n], red, stream)
+            recs = DeviceRecords(sc.keys, sc.key_end[:n], sc.vals, sc.val_end[:n])
+            if where is None:
+                f, nb = reduce_segments(recs, [0], [n], red, stream)
+                nbad[q] = nb[0]
+            else:   # the kept records are well-formed: the fold over them meets no bad value
+                from .where import filter_records
+                kept = filter_records(recs, where, None, stream)
+                f, _ = reduce_segments(kept.records, [0], [kept.nkept], red, stream)
+                nbad[q] = kept.nbad
+                nmatch[q] = kept.nkept
             fields[q] = f[0]
-            nbad[q] = nb[0]
             nrec[q] = n
             ends[q] = (sc.end, sc.err)
-        return ReduceBatch(red, fields, nrec, nbad, status, ends, n_large, n_fallback, stream)
+        return ReduceBatch(red, fields, nrec, nbad, status, ends, n_large, n_fallback, stream, nmatch)
 
-    def rollup(self, group, reduce, stream=None):
+    def rollup(self, group, reduce, stream=None, where=None):
         """The whole file rolled up: its records (iter()) grouped by `group` (a rollup.GroupBy), `reduce`
         folded over every group's values -> rollup.Rollup with one segment.  A file sorts its keys, so
         the group keys increase strictly and Rollup.write_file() gives the rolled-up .mtbl.  A scan
         that does not end cleanly raises as Merger sources do.  Everything runs on `stream` (default:
-        the current stream), which the call synchronises."""
+        the current stream), which the call synchronises.  where (a where.Where): only the records
+        whose value it keeps are rolled up (rollup_records)."""
         from .merger import _clean_scan
         from .rollup import rollup_records
         stream = self._s(stream)
         with torch.cuda.stream(stream):
-            return rollup_records(_clean_scan(self.iter()), group, reduce, None, stream)
+            return rollup_records(_clean_scan(self.iter()), group, reduce, None, stream, where)
 
-    def rollup_batch(self, queries, group, reduce, max_blocks: int = 64, stream=None):
+    def rollup_batch(self, queries, group, reduce, max_blocks: int = 64, stream=None, where=None):
         """scan_batch, then one rollup over its records with the queries as segments (seg_off =
         rec_off): per query, the records scan_batch reports for it grouped by `group` with `reduce`
         folded over every group -> rollup.Rollup, groups(q) per query.  A query the walk hands back
         (SCAN_LARGE, SCAN_FALLBACK) and every query of a reader with an irregular index is answered
         by the seek path and rolled up from its own device records, kept beside the kernel path's
         answer; end(q) / err(q) tell how such a query's iteration ended.  Everything runs on `stream`
-        (default: the current stream), which the call synchronises."""
+        (default: the current stream), which the call synchronises.  where (a where.Where): every
+        query's records are filtered first and the kept ones rolled up (rollup_records)."""
         from .encode import DeviceRecords
         from .reduce import as_reduce
         from .rollup import _as_group, rollup_records
+        from .where import as_where
         grp = _as_group(group)
         red = as_reduce(reduce)
         if red is None:
             raise ValueError(f"rollup_batch: {reduce!r} is not a Reduce")
+        where = as_where(where)
         stream = self._s(stream)
         with torch.cuda.stream(stream):
             sb = self._scan_batch(list(queries), max_blocks, None, stream)
-            out = rollup_records(DeviceRecords(sb.keys, sb.key_end, sb.vals, sb.val_end), grp, red, sb.rec_off, stream)
+            out = rollup_records(DeviceRecords(sb.keys, sb.key_end, sb.vals, sb.val_end), grp, red, sb.rec_off, stream,
+                                 where)
             for q, sc in sb._served.items():
                 n = sc.nrec
                 out._served[q] = rollup_records(DeviceRecords(sc.keys, sc.key_end[:n], sc.vals, sc.val_end[:n]), grp,
-                                                red, None, stream)
+                                                red, None, stream, where)
                 out._ends[q] = (sc.end, sc.err)
             return out
 

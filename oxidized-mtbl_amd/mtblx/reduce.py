@@ -254,13 +254,15 @@ class ReduceBatch:
     (the u64 bit patterns), `nrec` / `nbad` int64 [nq] (records yielded; those among them whose value
     is not 8 * F bytes long -- with a varint Reduce: not F varints --, left out and counted), `status` int32 [nq] (SCAN_* of the scan walk).
     A query the walk handed back (SCAN_LARGE, SCAN_FALLBACK, an irregular index) was answered by the
-    seek path and its device records reduced by reduce_segments: values(q) / value_bytes(q) give every
+    seek path and its device records reduced by reduce_segments (with a `where`: filtered first, and
+    `nmatch` int64 [nq] counts the values the predicate kept): values(q) / value_bytes(q) give every
     query's result, whichever path served it, and end(q) / err(q) how such a query's iteration ended
     (Scan.end / Scan.err; END_NONE for a kernel-served query)."""
 
-    def __init__(self, reduce, fields, nrec, nbad, status, ends, n_large, n_fallback, stream=None):
+    def __init__(self, reduce, fields, nrec, nbad, status, ends, n_large, n_fallback, stream=None, nmatch=None):
         self._stream = stream      # the stream of the batch: every host read goes through it
         self.reduce = reduce
+        self.nmatch = nmatch       # reduce_batch(where=): int64 [nq], the values the predicate kept; else None
         self.nq = int(nrec.numel())
         self.fields, self.nrec, self.nbad, self.status = fields, nrec, nbad, status
         self._ends = ends          # q -> (end, err) of the queries the seek path answered

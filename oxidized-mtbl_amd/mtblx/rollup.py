@@ -200,14 +200,17 @@ class Rollup:
                                  compression=compression)
 
 
-def rollup_records(records, group, reduce, seg_off=None, stream=None) -> Rollup:
+def rollup_records(records, group, reduce, seg_off=None, stream=None, where=None) -> Rollup:
     """`records` (an encode.DeviceRecords) grouped by `group` (a GroupBy) inside every segment, `reduce`
     (a Reduce or a shorthand name) folded over every group's values.  seg_off: int64 [nseg + 1] (device,
     or anything torch.as_tensor takes) with 0 = off[0] <= ... <= off[nseg] = n, else ValueError; None:
     one segment that holds everything.  mtblx_rollup_plan, a read-back of its two totals, one
     allocation sized from them, mtblx_rollup_emit, mtblx_reduce_segments over the groups and
     mtblx_reduce_encode: no record returns to the host.  Everything runs on `stream` (default: the
-    current stream), which the call synchronises."""
+    current stream), which the call synchronises.  where (a where.Where): the records are filtered
+    first (filter_records) and the kept ones rolled up with the kept segments (seg_off = {0,
+    seg_end...}); grp_rec then indexes the KEPT records and a bad value is dropped by the filter, so
+    nbad is 0 wherever the Where has the Reduce's layout."""
     import torch
 
     from . import _lib, codec
@@ -217,6 +220,10 @@ def rollup_records(records, group, reduce, seg_off=None, stream=None) -> Rollup:
     red = as_reduce(reduce)
     if red is None:
         raise ValueError(f"rollup: {reduce!r} is not a Reduce")
+    if where is not None:
+        from .where import as_where, filter_records
+        kept = filter_records(records, as_where(where), [0, records.n] if seg_off is None else seg_off, stream)
+        return rollup_records(kept.records, grp, red, kept.seg_off(), kept._stream, None)
     dev = records.key_end.device
     s = codec._stream_of(stream, dev)
     with torch.cuda.stream(s):

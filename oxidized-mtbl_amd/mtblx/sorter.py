@@ -301,24 +301,29 @@ class Sorter:
         self.merges += 1
 
     # ---- into_iter (:244-257)
-    def records(self) -> DeviceRecords:
-        """the sorted, merged stream on the device (what encode.write_file takes).  Consumes the Sorter."""
+    def records(self, where=None) -> DeviceRecords:
+        """the sorted, merged stream on the device (what encode.write_file takes).  Consumes the Sorter.
+        where (a where.Where): only the records whose MERGED value it keeps (filter_records)."""
         if self._done:
             raise RuntimeError("Sorter already consumed")
+        if where is not None:
+            from .where import as_where, filter_records
+            as_where(where)                                 # refused before the Sorter is consumed
         self._done = True
         self.write_chunk()                                  # :246, also when nothing is pending
-        return self._merge_all()                            # :253-256; no merge_chunks here
+        r = self._merge_all()                               # :253-256; no merge_chunks here
+        return r if where is None else filter_records(r, where, None, self._s()).records
 
     def into_iter(self):
         """MergerIter over the chunks: (key, merged value) per distinct key"""
         return iter(_records_list(self.records()))
 
     def write_file(self, block_size: int = 8192, restart_interval: int = 16,
-                   compression: int = CompressionType.None_) -> torch.Tensor:
-        """the .mtbl file (device uint8), written by the device Writer"""
+                   compression: int = CompressionType.None_, where=None) -> torch.Tensor:
+        """the .mtbl file (device uint8), written by the device Writer; where: as records(where=)"""
         s = self._s()
         with torch.cuda.stream(s):   # the last chunk, the merge and the Writer on one stream
-            return encode.write_file(self.records(), block_size, restart_interval, stream=s, compression=compression)
+            return encode.write_file(self.records(where), block_size, restart_interval, stream=s, compression=compression)
 
     def write_into(self, writer) -> None:
         """Sorter::write_into (:235-242) for the host Writer"""
