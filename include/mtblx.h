@@ -1286,6 +1286,49 @@ int mtblx_stream_copy(void* dst, const void* src, uint64_t bytes, int variant, v
 int mtblx_copy_ranges(const uint8_t* src, const uint64_t* src_off, uint8_t* dst, const uint64_t* dst_off,
                       const uint64_t* len, const uint64_t* chunk_base, uint32_t n, uint64_t nchunks, void* stream);
 
+/* ---- Diagnostics: a process-wide compute-unit limit for launch sizing ----
+ * Most launches cap their grid at a multiple of the device's compute units and let every
+ * workgroup, wave or lane loop over the rest of the work.  The second trip of such a loop needs,
+ * on a whole MI355X, inputs far above what a test can afford; this seam lowers the cap instead.
+ *
+ * mtblx_debug_cu_limit(n) stores n (one relaxed atomic; 0 = no limit, the default) and returns
+ * the previous value.  While a limit is set every launch is sized as if the device had
+ * min(real compute units, max(1, n)) of them, from the next launch of every kernel on (grids that
+ * are cached per device are recomputed, and nothing computed under a limit is cached).  The limit
+ * can only LOWER the count, never raise it: the decode kernels' look-back between workgroups needs
+ * every workgroup of a launch resident, and a grid above the device's real capacity could spin
+ * forever.  MTBLX_PIPE_CUS still applies; the limit applies on top of it.  No workspace size and no
+ * result depends on the limit: a plan made under one limit and its emit under another are valid.
+ * Not thread-safe against launches in flight on other host threads (they see either value).
+ *
+ * mtblx_debug_grid_items(family, arg) = the work items one launch of that family starts, at the
+ * current limit and the current routing variables, before a worker of its loop takes a second
+ * trip: n items with n > 2 * this make every worker wrap at least twice.  Computed by the same
+ * functions the launches use.  0 for an unknown family.
+ *
+ * mtblx_debug_decode_tiles = the tiles the block decode cuts a batch of nblk blocks, the longest
+ * max_blk_len bytes, into (verify: mtblx_decode_blocks_verify's plan), and in *kind (may be NULL)
+ * the kernel family that takes it: 0 the small pipeline, 1 the large one (MTBLX_GRID_DECODE_PIPE
+ * both), 2 k_decode_tiles (MTBLX_GRID_DECODE_TILES). */
+#define MTBLX_GRID_SCAN_PLAN 0     /* queries: k_scan_plan<...> of scan_plan / scan_reduce / scan_reduce_where */
+#define MTBLX_GRID_SCAN_EMIT 1     /* queries: k_scan_emit                                                      */
+#define MTBLX_GRID_GET 2           /* keys: k_get_lanes, or k_get with MTBLX_GET_KERNEL=wave                    */
+#define MTBLX_GRID_MERGE_BUILD 3   /* records: k_merge_build                                                    */
+#define MTBLX_GRID_SEG_BUILD 4     /* records: k_seg_build                                                      */
+#define MTBLX_GRID_SORT_SKIP 5     /* records: k_sort_skip                                                      */
+#define MTBLX_GRID_CRC 6           /* blocks: k_crc32c_mfma (64 per wave and trip), or k_crc32c_blocks with
+                                      MTBLX_CRC_KERNEL=lanes                                                    */
+#define MTBLX_GRID_SNAPPY_SMALL 7  /* blocks: the widest of k_snappy_quads / _exec / _waves / _deferred         */
+#define MTBLX_GRID_SNAPPY_LARGE 8  /* blocks: k_snappy_blocks<Large> (blocks above 4608 bytes)                  */
+#define MTBLX_GRID_SNAPPY_COMP 9   /* blocks: k_snappy_compress, k_frame_write                                  */
+#define MTBLX_GRID_COPY_RANGES 10  /* 16-byte chunks: k_copy_ranges                                             */
+#define MTBLX_GRID_STREAM_COPY 11  /* 16-byte chunks: k_stream_copy; arg = mtblx_stream_copy's variant          */
+#define MTBLX_GRID_DECODE_PIPE 12  /* tiles: k_decode_pipe<...>                                                 */
+#define MTBLX_GRID_DECODE_TILES 13 /* tiles: k_decode_tiles<CfgLarge>, or <CfgLargeP> with arg = 1 (positions)  */
+int mtblx_debug_cu_limit(int n);
+uint64_t mtblx_debug_grid_items(int family, int arg);
+uint32_t mtblx_debug_decode_tiles(uint32_t nblk, uint32_t max_blk_len, int verify, int* kind);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@
 namespace {
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+constexpr uint64_t kRangesU = 4;   // chunks in flight per thread of k_copy_ranges
 
 template <int U, bool NTS, bool NTL>
 __global__ void __launch_bounds__(256) k_stream_copy(const v4u* __restrict__ src, v4u* __restrict__ dst,
@@ -56,7 +57,7 @@ __global__ void __launch_bounds__(256) k_copy_ranges(const uint8_t* __restrict__
                                                      uint8_t* __restrict__ dst, const uint64_t* dst_off,
                                                      const uint64_t* len, const uint64_t* chunk_base, uint32_t n,
                                                      uint64_t nchunks) {
-  constexpr int U = 4;
+  constexpr int U = (int)kRangesU;
   const uint64_t stride = (uint64_t)gridDim.x * 256u;
   uint64_t c = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   for (; c < nchunks; c += stride * U) {
@@ -100,16 +101,25 @@ __global__ void __launch_bounds__(256) k_copy_ranges(const uint8_t* __restrict__
   }
 }
 
+// Launch sizes, shared with mtblx_debug_grid_items(): at most 8 workgroups of 256 threads per CU;
+// a thread of k_copy_ranges takes 4 chunks of 16 bytes per trip, one of k_stream_copy<U> takes U
+inline uint64_t copy_grid_cap() { return (uint64_t)mtblx_dev::cu_count() * 8u; }
+inline int stream_unroll(int variant) { return 1 << (variant & 3); }
+
 }  // namespace
+
+extern "C" uint64_t mtblx_grid_items_copy_ranges(void) { return copy_grid_cap() * 256u * kRangesU; }
+extern "C" uint64_t mtblx_grid_items_stream_copy(int variant) {
+  return copy_grid_cap() * 256u * (uint64_t)stream_unroll(variant);
+}
 
 extern "C" int mtblx_copy_ranges(const uint8_t* src, const uint64_t* src_off, uint8_t* dst, const uint64_t* dst_off,
                                  const uint64_t* len, const uint64_t* chunk_base, uint32_t n, uint64_t nchunks,
                                  void* stream) {
   if (n == 0 || nchunks == 0) return MTBLX_OK;
   if (!src || !src_off || !dst || !dst_off || !len || !chunk_base) return MTBLX_E_INVAL;
-  const int ncu = mtblx_dev::cu_count();
-  const uint64_t want = (nchunks + 4 * 256 - 1) / (4 * 256);
-  const dim3 g((unsigned)(want < (uint64_t)ncu * 8u ? want : (uint64_t)ncu * 8u));
+  const uint64_t want = (nchunks + kRangesU * 256 - 1) / (kRangesU * 256), cap = copy_grid_cap();
+  const dim3 g((unsigned)(want < cap ? want : cap));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   MTBLX_LAUNCH((src, MTBLX_R(src_off, 8ull * n), dst, MTBLX_R(dst_off, 8ull * n), MTBLX_R(len, 8ull * n),
                 MTBLX_R(chunk_base, 8ull * n)),
@@ -120,16 +130,15 @@ extern "C" int mtblx_copy_ranges(const uint8_t* src, const uint64_t* src_off, ui
 extern "C" int mtblx_stream_copy(void* dst, const void* src, uint64_t bytes, int variant, void* stream) {
   if (!dst || !src || (bytes & 15u) || ((uintptr_t)dst & 15u) || ((uintptr_t)src & 15u)) return MTBLX_E_INVAL;
   if (bytes == 0) return MTBLX_OK;
-  const int ncu = mtblx_dev::cu_count();
   const uint64_t n16 = bytes / 16u;
-  const dim3 g((unsigned)ncu * 8u);
+  const dim3 g((unsigned)copy_grid_cap());
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const v4u* sp = static_cast<const v4u*>(src);
   v4u* dp = static_cast<v4u*>(dst);
-  switch (variant & 3) {
-    case 0: launch<1>(variant, g, s, sp, dp, n16); break;
-    case 1: launch<2>(variant, g, s, sp, dp, n16); break;
-    case 2: launch<4>(variant, g, s, sp, dp, n16); break;
+  switch (stream_unroll(variant)) {
+    case 1: launch<1>(variant, g, s, sp, dp, n16); break;
+    case 2: launch<2>(variant, g, s, sp, dp, n16); break;
+    case 4: launch<4>(variant, g, s, sp, dp, n16); break;
     default: launch<8>(variant, g, s, sp, dp, n16); break;
   }
   return hipGetLastError() == hipSuccess ? MTBLX_OK : MTBLX_E_HIP;

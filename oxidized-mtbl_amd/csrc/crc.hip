@@ -517,7 +517,31 @@ __global__ void __launch_bounds__(kMThreads, 1) k_crc32c_mfma(const uint8_t* __r
 // Removing the bank conflicts (3, 5, 7) or the scattered window loads (6) did not pay: the
 // kernel is not bound by either alone, and every variant added vector instructions per byte.
 
+// Launch sizes, shared by mtblx_crc32c_blocks and mtblx_debug_grid_items().
+// The matrix-core kernel unless MTBLX_CRC_KERNEL=lanes (read per call).
+inline bool mfma_routing() {
+  const char* kv = getenv("MTBLX_CRC_KERNEL");
+  return !kv || kv[0] != 'l';
+}
+// k_crc32c_mfma is persistent: one 16-wave workgroup (160 KiB LDS) per CU; a wave takes a window of
+// kWave blocks (one per lane) per trip of its outer loop
+inline uint32_t mfma_grid_cap() { return (uint32_t)mtblx_dev::cu_count(); }
+// k_crc32c_blocks, 98 VGPRs: one 1024-thread workgroup is resident per CU, so a grid of one
+// workgroup per CU runs in a single round; 2 per CU measured 0.1256-0.1261 ms against 0.1232
+// (profiles/r03/final2)
+#ifndef MTBLX_CRC_WG_PER_CU
+#define MTBLX_CRC_WG_PER_CU 1
+#endif
+constexpr uint32_t kLanesWaves = kCrcThreads / kWave;   // waves (blocks in flight) per workgroup
+inline uint32_t lanes_grid_cap() { return (uint32_t)mtblx_dev::cu_count() * MTBLX_CRC_WG_PER_CU; }
+
 }  // namespace mtblx_crc
+
+extern "C" uint64_t mtblx_grid_items_crc(void) {
+  // a wave of k_crc32c_mfma takes a window of kWave blocks (one per lane) per trip
+  return mtblx_crc::mfma_routing() ? (uint64_t)mtblx_crc::mfma_grid_cap() * mtblx_crc::kMWaves * mtblx_crc::kWave
+                                   : (uint64_t)mtblx_crc::lanes_grid_cap() * mtblx_crc::kLanesWaves;
+}
 
 extern "C" int mtblx_crc32c_blocks(const mtblx_block_batch* in, uint32_t* crc, uint8_t* bad, int framed,
                                    void* stream) {
@@ -526,11 +550,10 @@ extern "C" int mtblx_crc32c_blocks(const mtblx_block_batch* in, uint32_t* crc, u
   if (!in->data || !in->blk_off || !in->blk_len) return MTBLX_E_INVAL;
   // the matrix-core kernel unless MTBLX_CRC_KERNEL=lanes (the VALU table kernel, kept for A/B):
   // 0.102 vs 0.120 ms on cfg2 (profiles/r04/crc_mfma)
-  const char* kv = getenv("MTBLX_CRC_KERNEL");
-  if (!kv || kv[0] != 'l') {
-    const int mgrid = mtblx_dev::cu_count();   // persistent: one 16-wave workgroup (160 KiB LDS) per CU
+  if (mtblx_crc::mfma_routing()) {
+    const uint32_t mgrid = mtblx_crc::mfma_grid_cap();
     const uint32_t need = (in->nblk + mtblx_crc::kMWaves - 1u) / mtblx_crc::kMWaves;
-    const dim3 g(need < (uint32_t)mgrid ? need : (uint32_t)mgrid), t(mtblx_crc::kMThreads);
+    const dim3 g(need < mgrid ? need : mgrid), t(mtblx_crc::kMThreads);
     MTBLX_LAUNCH((MTBLX_R(in->data, in->data_len), MTBLX_R(in->blk_off, 8ull * in->nblk),
                   MTBLX_R(in->blk_len, 4ull * in->nblk), MTBLX_R(crc, 4ull * in->nblk), MTBLX_R(bad, in->nblk)),
                  mtblx_crc::k_crc32c_mfma, g, t, 0,
@@ -538,15 +561,10 @@ extern "C" int mtblx_crc32c_blocks(const mtblx_block_batch* in, uint32_t* crc, u
                        in->data_len, in->blk_off, in->blk_len, in->nblk, crc, bad, framed);
     return hipGetLastError() == hipSuccess ? MTBLX_OK : MTBLX_E_HIP;
   }
-// 98 VGPRs: one 1024-thread workgroup is resident per CU, so a grid of one workgroup per CU runs
-// in a single round; 2 per CU measured 0.1256-0.1261 ms against 0.1232 (profiles/r03/final2)
-#ifndef MTBLX_CRC_WG_PER_CU
-#define MTBLX_CRC_WG_PER_CU 1
-#endif
-  const int grid = mtblx_dev::cu_count() * MTBLX_CRC_WG_PER_CU;
-  const uint32_t wpg = mtblx_crc::kCrcThreads / mtblx_crc::kWave;   // waves (blocks in flight) per workgroup
+  const uint32_t grid = mtblx_crc::lanes_grid_cap();
+  const uint32_t wpg = mtblx_crc::kLanesWaves;
   const uint32_t need = (in->nblk + wpg - 1u) / wpg;
-  const dim3 g(need < (uint32_t)grid ? need : (uint32_t)grid), t(mtblx_crc::kCrcThreads);
+  const dim3 g(need < grid ? need : grid), t(mtblx_crc::kCrcThreads);
   MTBLX_LAUNCH((MTBLX_R(in->data, in->data_len), MTBLX_R(in->blk_off, 8ull * in->nblk),
                 MTBLX_R(in->blk_len, 4ull * in->nblk), MTBLX_R(crc, 4ull * in->nblk), MTBLX_R(bad, in->nblk)),
                mtblx_crc::k_crc32c_blocks, g, t, 0,

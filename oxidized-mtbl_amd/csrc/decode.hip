@@ -2528,21 +2528,24 @@ Plan make_plan(uint32_t nblk, uint32_t max_len, bool verify) {
 // One workgroup per CU: every workgroup of a launch is resident, which the look-back between
 // workgroups needs.  MTBLX_PIPE_CUS caps it (diagnostic: several processes sharing one GPU, e.g.
 // bench.py --share-gpu, each keep their launches co-resident on their share of the CUs).
-int pipe_grid(uint32_t ntiles) {
+// The *_cap functions are the largest grid (the tiles a launch starts before a workgroup takes its
+// second one); the launches and mtblx_debug_grid_items() share them.  Cached per device, except
+// under the diagnostic CU limit (devinfo.h), which lowers them from the next launch on.
+int pipe_grid_cap() {
   static mtblx_dev::Cache cache;
-  const int g = cache.get([] {
+  return cache.get([] {
     int ncu = mtblx_dev::cu_count();
     const char* cap = getenv("MTBLX_PIPE_CUS");
     if (cap && atoi(cap) > 0) ncu = std::min(ncu, atoi(cap));
     return std::max(1, std::min(ncu, kMaxLookbackLoads * kWave + 1));
   });
-  return (int)std::min<uint32_t>(ntiles, (uint32_t)g);
 }
+int pipe_grid(uint32_t ntiles) { return (int)std::min<uint32_t>(ntiles, (uint32_t)pipe_grid_cap()); }
 
 template <class C>
-int resident_grid(uint32_t ntiles) {
+int resident_grid_cap() {
   static mtblx_dev::Cache cache;
-  const int g = cache.get([] {
+  return cache.get([] {
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_decode_tiles<C>, kThreads, 0) != hipSuccess || occ < 1)
       occ = 1;
@@ -2551,9 +2554,24 @@ int resident_grid(uint32_t ntiles) {
     const int c = std::max(1, mtblx_dev::cu_count() * std::min(occ, lds_lim));
     return std::min(c, kMaxLookbackLoads * kThreads + 1);  // look-back window = G - 1
   });
-  return (int)std::min<uint32_t>(ntiles, (uint32_t)g);
+}
+template <class C>
+int resident_grid(uint32_t ntiles) {
+  return (int)std::min<uint32_t>(ntiles, (uint32_t)resident_grid_cap<C>());
 }
 }  // namespace
+
+// diagnostics (mtblx_debug_grid_items, mtblx_debug_decode_tiles): the grid caps in tiles, and the
+// kernel family (0 pipe small, 1 pipe large, 2 tiles) and tile count make_plan gives a batch
+extern "C" uint64_t mtblx_grid_items_decode_pipe(void) { return (uint64_t)pipe_grid_cap(); }
+extern "C" uint64_t mtblx_grid_items_decode_tiles(int positions) {
+  return (uint64_t)(positions ? resident_grid_cap<CfgLargeP>() : resident_grid_cap<CfgLarge>());
+}
+extern "C" uint32_t mtblx_impl_decode_tiles(uint32_t nblk, uint32_t max_blk_len, int verify, int* kind) {
+  const Plan p = make_plan(nblk, max_blk_len, verify != 0);
+  if (kind) *kind = p.kind;
+  return p.ntiles;
+}
 
 // workspace: [0, 128) diagnostic stamps | [128, 256) WsHdr | 3 u64 per tile (tiles <= nblk).
 // Zero-filled once by the caller; every launch leaves it ready for the next (ws_end).

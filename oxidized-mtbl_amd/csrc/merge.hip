@@ -38,18 +38,25 @@ namespace {
 
 __global__ void __launch_bounds__(64) k_merge_prefix(SrcTab t, uint64_t* hdr) {
   if (threadIdx.x || blockIdx.x) return;
-  bool have = false;
-  Key mn{nullptr, 0}, mx{nullptr, 0};
+  // the sources holding the smallest first key and the largest last key, by their numbers (nsrc:
+  // none yet); the two keys are read again from the table once the sources are known.
+  // Deliberately NOT two Key structs updated in the loop ("if (!have || key_cmp(f, mn, 0) < 0) mn = f;"):
+  // that form was compiled for gfx950 into code that assigned mn.p on the first source's path only
+  // ("Looping launches"; regression: tests/test_grid_wrap_gpu.py::test_merge_records)
+  uint32_t smin = t.nsrc, smax = t.nsrc;
   for (uint32_t s = 0; s < t.nsrc; ++s) {
     const uint32_t n = t.base[s + 1] - t.base[s];
     if (!n) continue;
-    const Key f = key_of(t, s, 0), l = key_of(t, s, n - 1);
-    if (!have || key_cmp(f, mn, 0) < 0) mn = f;
-    if (!have || key_cmp(l, mx, 0) > 0) mx = l;
-    have = true;
+    if (smin == t.nsrc) {
+      smin = smax = s;
+      continue;
+    }
+    if (key_cmp(key_of(t, s, 0), key_of(t, smin, 0), 0) < 0) smin = s;
+    if (key_cmp(key_of(t, s, n - 1), key_of(t, smax, t.base[smax + 1] - t.base[smax] - 1), 0) > 0) smax = s;
   }
   uint64_t skip = 0;
-  if (have) {
+  if (smin != t.nsrc) {
+    const Key mn = key_of(t, smin, 0), mx = key_of(t, smax, t.base[smax + 1] - t.base[smax] - 1);
     const uint64_t m = mn.len < mx.len ? mn.len : mx.len;
     while (skip < m && mn.p[skip] == mx.p[skip]) ++skip;
   }
@@ -92,6 +99,8 @@ extern "C" int mtblx_merge_impl_select_ok(const mtblx_select* sel, uint32_t nsrc
 // arguments already checked (mtblx_api.cpp): ws 256-byte aligned and large enough, nsrc <= 64
 // phase_ms (diagnostic, may be NULL): HIP-event times of [0] the handle build (prefix, handles, order
 // check), [1 .. passes] the merge passes, [passes + 1] the grouping; phase_cap >= passes + 2
+extern "C" uint64_t mtblx_grid_items_merge_build(void) { return build_grid_cap() * kThreads; }
+
 // sel (may be NULL: no selection, totals is 6 words): the rule of mtblx_merge_plan_select, totals 8 words
 extern "C" int mtblx_merge_impl_plan(const mtblx_records* src, uint32_t nsrc, const mtblx_select* sel,
                                      uint64_t* totals, void* ws, hipStream_t s, float* phase_ms,
@@ -116,7 +125,7 @@ extern "C" int mtblx_merge_impl_plan(const mtblx_records* src, uint32_t nsrc, co
   const dim3 b(kThreads);
   ev.mark(s);
   if (n) {
-    const uint64_t want = ((uint64_t)n + kThreads - 1) / kThreads, cap = (uint64_t)mtblx_dev::cu_count() * 16u;
+    const uint64_t want = ((uint64_t)n + kThreads - 1) / kThreads, cap = build_grid_cap();
     MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_merge_prefix, dim3(1), dim3(64), 0, s, t, hdr);
     MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_merge_build, dim3((unsigned)(want < cap ? want : cap)), b, 0, s, t, hdr,
                  hb[0], n);

@@ -48,6 +48,11 @@ constexpr uint64_t kMagic = 0x4d54424c584d5247ull;
 // the Sorter's planned mark differs from the Merger's in bits no record or source count reaches
 constexpr uint64_t kSortMagic = 0x5354424c58535254ull;
 
+// workgroups of the handle-building launches (k_merge_build, k_seg_build, k_sort_skip): kThreads
+// records per workgroup and trip, at most 16 workgroups per CU.  The launches and
+// mtblx_debug_grid_items() share it.
+inline uint64_t build_grid_cap() { return (uint64_t)mtblx_dev::cu_count() * 16u; }
+
 // workspace header words (u64)
 enum { H_GROUPS = 0, H_KEYB, H_NVAL, H_VALB, H_DROPPED, H_FLAGS, H_SKIP, H_PLANNED, H_FIRSTB, H_LASTB,
        H_SEGSKIP,   // merge_seg.hip: u64 words from the header to the per-segment skip array

@@ -248,6 +248,7 @@ unsigned blocks_for(uint64_t items) { return items ? (unsigned)((items + kThread
 }  // namespace
 
 extern "C" size_t mtblx_merge_seg_impl_ws_bytes(uint64_t nrec, uint32_t nseg) { return seg_layout(nrec, nseg).total; }
+extern "C" uint64_t mtblx_grid_items_seg_build(void) { return build_grid_cap() * kThreads; }
 
 // arguments already checked (mtblx_api.cpp): ws 256-byte aligned and large enough, nsrc <= 64,
 // nseg <= MTBLX_MERGE_MAX_SEGMENTS, no NULL seg_off entry.  phase_ms (diagnostic, may be NULL):
@@ -287,7 +288,7 @@ extern "C" int mtblx_merge_seg_impl_plan(const mtblx_records* src, const uint64_
     MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_seg_check, dim3(blocks_for((uint64_t)nseg + 1)), b, 0, s, t, g, hdr, nseg,
                  (uint64_t)((S.skip - L.hdr) / 8));
     if (n) {
-      const uint64_t want = blocks_for(n), cap = (uint64_t)mtblx_dev::cu_count() * 16u;
+      const uint64_t want = blocks_for(n), cap = build_grid_cap();
       MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_seg_skip, dim3(blocks_for(nseg)), b, 0, s, t, g, hdr, skip, nseg);
       MTBLX_LAUNCH((MTBLX_R(w, S.total)), k_seg_build, dim3((unsigned)(want < cap ? want : cap)), b, 0, s, t, g, hdr,
                    skip, hb[0], n, nseg);

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "mtblx.h"
+#include "devinfo.h"
 
 extern "C" size_t mtblx_impl_ws_bytes(uint32_t nblk);
 extern "C" int mtblx_impl_run(const mtblx_block_batch* in, const mtblx_decoded* out, void* ws, size_t ws_bytes,
@@ -18,6 +19,51 @@ extern "C" int mtblx_impl_run_valpos(const mtblx_block_batch* in, const mtblx_de
                                      size_t ws_bytes, hipStream_t s);
 
 extern "C" int mtblx_abi_version(void) { return MTBLX_ABI_VERSION; }
+
+// ---- diagnostics: the CU limit of devinfo.h and what each capped launch starts under it ----
+extern "C" uint64_t mtblx_grid_items_scan_plan(void);
+extern "C" uint64_t mtblx_grid_items_scan_emit(void);
+extern "C" uint64_t mtblx_grid_items_get(void);
+extern "C" uint64_t mtblx_grid_items_merge_build(void);
+extern "C" uint64_t mtblx_grid_items_seg_build(void);
+extern "C" uint64_t mtblx_grid_items_sort_skip(void);
+extern "C" uint64_t mtblx_grid_items_crc(void);
+extern "C" uint64_t mtblx_grid_items_snappy_small(void);
+extern "C" uint64_t mtblx_grid_items_snappy_large(void);
+extern "C" uint64_t mtblx_grid_items_snappy_comp(void);
+extern "C" uint64_t mtblx_grid_items_copy_ranges(void);
+extern "C" uint64_t mtblx_grid_items_stream_copy(int variant);
+extern "C" uint64_t mtblx_grid_items_decode_pipe(void);
+extern "C" uint64_t mtblx_grid_items_decode_tiles(int positions);
+extern "C" uint32_t mtblx_impl_decode_tiles(uint32_t nblk, uint32_t max_blk_len, int verify, int* kind);
+
+extern "C" int mtblx_debug_cu_limit(int n) {
+  return mtblx_dev::cu_limit_word().exchange(n, std::memory_order_relaxed);
+}
+
+extern "C" uint64_t mtblx_debug_grid_items(int family, int arg) {
+  switch (family) {
+    case MTBLX_GRID_SCAN_PLAN: return mtblx_grid_items_scan_plan();
+    case MTBLX_GRID_SCAN_EMIT: return mtblx_grid_items_scan_emit();
+    case MTBLX_GRID_GET: return mtblx_grid_items_get();
+    case MTBLX_GRID_MERGE_BUILD: return mtblx_grid_items_merge_build();
+    case MTBLX_GRID_SEG_BUILD: return mtblx_grid_items_seg_build();
+    case MTBLX_GRID_SORT_SKIP: return mtblx_grid_items_sort_skip();
+    case MTBLX_GRID_CRC: return mtblx_grid_items_crc();
+    case MTBLX_GRID_SNAPPY_SMALL: return mtblx_grid_items_snappy_small();
+    case MTBLX_GRID_SNAPPY_LARGE: return mtblx_grid_items_snappy_large();
+    case MTBLX_GRID_SNAPPY_COMP: return mtblx_grid_items_snappy_comp();
+    case MTBLX_GRID_COPY_RANGES: return mtblx_grid_items_copy_ranges();
+    case MTBLX_GRID_STREAM_COPY: return mtblx_grid_items_stream_copy(arg);
+    case MTBLX_GRID_DECODE_PIPE: return mtblx_grid_items_decode_pipe();
+    case MTBLX_GRID_DECODE_TILES: return mtblx_grid_items_decode_tiles(arg);
+    default: return 0;
+  }
+}
+
+extern "C" uint32_t mtblx_debug_decode_tiles(uint32_t nblk, uint32_t max_blk_len, int verify, int* kind) {
+  return mtblx_impl_decode_tiles(nblk, max_blk_len, verify, kind);
+}
 
 extern "C" int mtblx_device_ok(void) {
   int dev = 0;

@@ -688,16 +688,25 @@ extern "C" int mtblx_block_dir(const uint8_t* file, uint64_t file_len, uint32_t 
   return hipGetLastError() == hipSuccess ? MTBLX_OK : MTBLX_E_HIP;
 }
 
-// k_get_lanes (one lane per query) unless MTBLX_GET_KERNEL=wave (k_get, one wave per query: A/B)
+// k_get_lanes (one lane per query) unless MTBLX_GET_KERNEL=wave (k_get, one wave per query: A/B).
+// The launch and mtblx_debug_grid_items() share the routing, the queries per workgroup and trip,
+// and the cap of the grid.
+static int get_wave_routing() {
+  const char* ge = getenv("MTBLX_GET_KERNEL");   // A/B knob, read per call
+  return ge && ge[0] == 'w' ? 1 : 0;
+}
+static uint64_t get_per_wg(int wave) { return wave ? 4u : 256u; }
+static uint64_t get_grid_cap() { return (uint64_t)mtblx_dev::cu_count() * 8u; }
+extern "C" uint64_t mtblx_grid_items_get(void) { return get_grid_cap() * get_per_wg(get_wave_routing()); }
+
 static void get_launch(const uint8_t* file, uint64_t file_len, uint32_t version, int verify, uint64_t index_off,
                        uint64_t index_len, mtblx_rd::DecTab tab, const uint8_t* keys, const uint64_t* key_end,
                        uint32_t nq, int32_t* status, uint64_t* val_off, uint64_t* val_len, hipStream_t s) {
-  const int grid = mtblx_dev::cu_count() * 8;
-  const char* ge = getenv("MTBLX_GET_KERNEL");   // A/B knob, read per call
-  const int wave = ge && ge[0] == 'w' ? 1 : 0;
-  const uint64_t per = wave ? 4u : 256u;   // queries per workgroup per pass
+  const uint64_t grid = get_grid_cap();
+  const int wave = get_wave_routing();
+  const uint64_t per = get_per_wg(wave);   // queries per workgroup per pass
   const uint64_t need = (nq + per - 1) / per;
-  const dim3 g((unsigned)(need < (uint64_t)grid ? need : (uint64_t)grid));
+  const dim3 g((unsigned)(need < grid ? need : grid));
   const uint64_t ntab = tab.dec ? tab.n : 0;
   if (wave) {
     MTBLX_LAUNCH((MTBLX_R(file, file_len), MTBLX_R(tab.start, 8ull * ntab), MTBLX_R(tab.doff, 8ull * ntab),

@@ -526,6 +526,13 @@ __global__ void __launch_bounds__(64) k_scan_emit(const uint8_t* file, uint64_t 
   }
 }
 
+// Launch sizes.  k_scan_plan: kPlanWaves queries (one per wave) per workgroup and trip, at most 8
+// workgroups per CU; k_scan_emit: one query per workgroup and trip, at most 16 per CU.  The
+// launches and mtblx_debug_grid_items() share these.
+constexpr uint64_t kPlanWaves = 256 / 64;
+inline uint64_t plan_grid_cap() { return (uint64_t)mtblx_dev::cu_count() * 8u; }
+inline uint64_t emit_grid_cap() { return (uint64_t)mtblx_dev::cu_count() * 16u; }
+
 }  // namespace mtblx_rd
 
 extern "C" size_t mtblx_scan_impl_ws_bytes(uint32_t nq) { return mtblx_rd::layout(nq).total; }
@@ -595,7 +602,7 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
   Land* land = reinterpret_cast<Land*>(w + L.land);
   if (hipMemsetAsync(hdr, 0, 8 * H_WORDS, s) != hipSuccess) return MTBLX_E_HIP;
   if (hipMemcpyAsync(dtype, type, 4ull * nq, hipMemcpyHostToDevice, s) != hipSuccess) return MTBLX_E_HIP;
-  const uint64_t need = ((uint64_t)nq + 3u) / 4u, cap = (uint64_t)mtblx_dev::cu_count() * 8u;
+  const uint64_t need = ((uint64_t)nq + kPlanWaves - 1u) / kPlanWaves, cap = plan_grid_cap();
   const uint64_t ntab = tab.dec ? tab.n : 0;
   (void)ntab;   // read by the bounds-checked build only
   if (where && varint)
@@ -651,6 +658,10 @@ extern "C" int mtblx_scan_impl_reduce(const uint8_t* file, uint64_t file_len, ui
   return MTBLX_OK;
 }
 
+// queries one launch starts before a wave (plan) or a workgroup (emit) takes its second one
+extern "C" uint64_t mtblx_grid_items_scan_plan(void) { return mtblx_rd::plan_grid_cap() * mtblx_rd::kPlanWaves; }
+extern "C" uint64_t mtblx_grid_items_scan_emit(void) { return mtblx_rd::emit_grid_cap(); }
+
 extern "C" int mtblx_scan_impl_emit(const uint8_t* file, uint64_t file_len, uint32_t version, uint64_t index_off,
                                     uint64_t index_len, const uint64_t* tab_start, const uint64_t* tab_doff,
                                     const uint64_t* tab_dlen, const int32_t* tab_st, uint32_t ntab_in,
@@ -662,7 +673,7 @@ extern "C" int mtblx_scan_impl_emit(const uint8_t* file, uint64_t file_len, uint
   const Layout L = layout(nq);
   const uint8_t* w = static_cast<const uint8_t*>(ws);
   if (hipMemsetAsync(out->flags, 0, 4, s) != hipSuccess) return MTBLX_E_HIP;
-  const uint64_t cap = (uint64_t)mtblx_dev::cu_count() * 16u;
+  const uint64_t cap = emit_grid_cap();
   const uint64_t ntab = tab.dec ? tab.n : 0;
   (void)ntab;   // read by the bounds-checked build only
   MTBLX_LAUNCH((MTBLX_R(file, file_len), MTBLX_R(tab.start, 8ull * ntab), MTBLX_R(tab.doff, 8ull * ntab),

@@ -347,13 +347,18 @@ __global__ void __launch_bounds__(kThreads) k_frame_write(const uint8_t* __restr
   }
 }
 
-inline dim3 wave_grid(uint32_t nblk) {   // one wave per block, at most two workgroups per CU (LDS)
+// one wave per block, at most two workgroups per CU (LDS); shared with mtblx_debug_grid_items()
+inline uint32_t wave_grid_cap() { return (uint32_t)mtblx_dev::cu_count() * 2u; }
+inline dim3 wave_grid(uint32_t nblk) {
   const uint32_t need = (nblk + kWaves - 1u) / kWaves;
-  const uint32_t cap = (uint32_t)mtblx_dev::cu_count() * 2u;
+  const uint32_t cap = wave_grid_cap();
   return dim3(need < cap ? need : cap);
 }
 
 }  // namespace mtblx_sc
+
+// blocks a k_snappy_compress / k_frame_write launch starts before a wave takes its second one
+extern "C" uint64_t mtblx_grid_items_snappy_comp(void) { return (uint64_t)mtblx_sc::wave_grid_cap() * mtblx_sc::kWaves; }
 
 extern "C" size_t mtblx_snappy_compress_workspace_bytes(uint32_t nblk) { return 4ull * nblk + 256; }
 

@@ -1836,14 +1836,28 @@ __global__ void __launch_bounds__(kDirThreads) k_snap_off(const uint32_t* dst_le
   }
 }
 
+// Launch sizes, shared by mtblx_snappy_decompress_dev and mtblx_debug_grid_items(): the capped
+// kernels' workgroups per CU, and the units (quads, rows of 64 blocks, blocks) a grid covers per trip
+constexpr int kDeferredWgPerCu = 2, kLargeWgPerCu = 2;
+uint32_t grid_cap(int per_cu) { return (uint32_t)(mtblx_dev::cu_count() * per_cu); }
 int grid_for(int per_cu, uint32_t units) {
-  const uint32_t g = (uint32_t)(mtblx_dev::cu_count() * per_cu);
+  const uint32_t g = grid_cap(per_cu);
   return (int)(units < g ? (units ? units : 1u) : g);
 }
 
 }  // namespace mtblx_snap
 
 using namespace mtblx_snap;
+
+// blocks per trip of the widest capped kernel a batch of small blocks (max_dst_len <= quad::OUT)
+// can meet -- k_snappy_quads / k_snappy_exec: NG blocks per workgroup, k_snappy_waves: one,
+// k_snappy_deferred: kWave -- and of k_snappy_blocks<Large> (one block per wave)
+extern "C" uint64_t mtblx_grid_items_snappy_small(void) {
+  const uint64_t q = (uint64_t)grid_cap(quad::WG_PER_CU) * quad::NG, w = grid_cap(MTBLX_WAVEP_WG_PER_CU),
+                 d = (uint64_t)grid_cap(kDeferredWgPerCu) * kWave;
+  return q > w ? (q > d ? q : d) : (w > d ? w : d);
+}
+extern "C" uint64_t mtblx_grid_items_snappy_large(void) { return (uint64_t)grid_cap(kLargeWgPerCu) * Large::WAVES; }
 
 extern "C" size_t mtblx_snappy_workspace_bytes(uint32_t nblk) {
   return 8u * ((size_t)(nblk + kDirSpan - 1) / kDirSpan + 1);
@@ -1911,10 +1925,10 @@ extern "C" int mtblx_snappy_decompress_dev(const uint8_t* src, const uint64_t* s
       MTBLX_LAUNCH((src, MTBLX_R(src_off, 8ull * nblk), MTBLX_R(src_len, 4ull * nblk), dst, MTBLX_R(dst_off, 8ull * nblk), MTBLX_R(dst_len, 4ull * nblk), MTBLX_R(status, 4ull * nblk), MTBLX_R(dec_len, 4ull * nblk)), lanes::k_snappy_lanes, glanes, tlanes, 0, s, src, src_off, src_len, nblk, dst, dst_off,
                          dst_len, status, dec_len, 1);
     }
-    MTBLX_LAUNCH((src, MTBLX_R(src_off, 8ull * nblk), MTBLX_R(src_len, 4ull * nblk), dst, MTBLX_R(dst_off, 8ull * nblk), MTBLX_R(dst_len, 4ull * nblk), MTBLX_R(status, 4ull * nblk), MTBLX_R(dec_len, 4ull * nblk)), quad::k_snappy_deferred, dim3(grid_for(2, (nblk + kWave - 1) / kWave)), dim3(kWave), 0, s,
+    MTBLX_LAUNCH((src, MTBLX_R(src_off, 8ull * nblk), MTBLX_R(src_len, 4ull * nblk), dst, MTBLX_R(dst_off, 8ull * nblk), MTBLX_R(dst_len, 4ull * nblk), MTBLX_R(status, 4ull * nblk), MTBLX_R(dec_len, 4ull * nblk)), quad::k_snappy_deferred, dim3(grid_for(kDeferredWgPerCu, (nblk + kWave - 1) / kWave)), dim3(kWave), 0, s,
                        src, src_off, src_len, nblk, dst, dst_off, dst_len, status, dec_len);
   } else {
-    MTBLX_LAUNCH((src, MTBLX_R(src_off, 8ull * nblk), MTBLX_R(src_len, 4ull * nblk), dst, MTBLX_R(dst_off, 8ull * nblk), MTBLX_R(dst_len, 4ull * nblk), MTBLX_R(status, 4ull * nblk), MTBLX_R(dec_len, 4ull * nblk)), k_snappy_blocks<Large>, dim3(grid_for(2, nblk)), dim3(Large::WAVES * kWave), 0, s, src,
+    MTBLX_LAUNCH((src, MTBLX_R(src_off, 8ull * nblk), MTBLX_R(src_len, 4ull * nblk), dst, MTBLX_R(dst_off, 8ull * nblk), MTBLX_R(dst_len, 4ull * nblk), MTBLX_R(status, 4ull * nblk), MTBLX_R(dec_len, 4ull * nblk)), k_snappy_blocks<Large>, dim3(grid_for(kLargeWgPerCu, (nblk + Large::WAVES - 1) / Large::WAVES)), dim3(Large::WAVES * kWave), 0, s, src,
                        src_off, src_len, nblk, dst, dst_off, dst_len, status, dec_len);
   }
   return hipGetLastError() == hipSuccess ? MTBLX_OK : MTBLX_E_HIP;

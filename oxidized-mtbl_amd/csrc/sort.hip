@@ -121,6 +121,7 @@ uint64_t sort_mark(uint64_t n) { return kSortMagic ^ n; }
 }  // namespace
 
 extern "C" size_t mtblx_sort_impl_ws_bytes(uint64_t nrec) { return layout(nrec).total; }
+extern "C" uint64_t mtblx_grid_items_sort_skip(void) { return build_grid_cap() * kThreads; }
 
 // arguments already checked (mtblx_api.cpp): ws 256-byte aligned and large enough
 // phase_ms (diagnostic, may be NULL): HIP-event times of [0] the shared-prefix scan, [1] the tile
@@ -149,7 +150,7 @@ extern "C" int mtblx_sort_impl_plan(const mtblx_records* in, uint64_t* totals, v
   const Handle* hf = hb[np & 1];
   ev.mark(s);
   if (n) {
-    const uint64_t want = ((uint64_t)n + kThreads - 1) / kThreads, cap = (uint64_t)mtblx_dev::cu_count() * 16u;
+    const uint64_t want = ((uint64_t)n + kThreads - 1) / kThreads, cap = build_grid_cap();
     MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_sort_skip, dim3((unsigned)(want < cap ? want : cap)), b, 0, s, t, hdr, n);
     ev.mark(s);
     MTBLX_LAUNCH((MTBLX_R(w, L.total)), k_sort_tile, dim3(sort_tiles(n)), b, 0, s, t, hdr, hb[0], n);

@@ -58,6 +58,7 @@ EXPORTS = [
     "mtblx_scan_reduce_where",
     "mtblx_stage_workspace_bytes", "mtblx_stage_plan", "mtblx_stage_emit", "mtblx_scan_touch", "mtblx_bitmap_compact",
     "mtblx_table_gather", "mtblx_dir_ascends",
+    "mtblx_debug_cu_limit", "mtblx_debug_grid_items", "mtblx_debug_decode_tiles",
 ]
 MERGE_MAX_SOURCES, MERGE_MAX_RECORDS = 64, (1 << 32) - 16
 MERGE_GROUPS, MERGE_CONCAT, MERGE_FIRST, MERGE_LAST = range(4)
@@ -82,6 +83,10 @@ SCAN_OK, SCAN_LARGE, SCAN_FALLBACK = range(3)  # mtblx_scan_result.status
 SCAN_MAX_KEY = 1024                            # MTBLX_SCAN_MAX_KEY: the emit kernel's key buffer
 SCAN_OVERFLOW, SCAN_NOT_PLANNED, SCAN_INTERNAL = 1, 2, 4   # *flags of mtblx_scan_emit
 SCAN_FROM, SCAN_GET, SCAN_PREFIX, SCAN_RANGE = range(4)    # query types (mtblx_key_filter's numbering)
+# MTBLX_GRID_*: the families of mtblx_debug_grid_items
+(GRID_SCAN_PLAN, GRID_SCAN_EMIT, GRID_GET, GRID_MERGE_BUILD, GRID_SEG_BUILD, GRID_SORT_SKIP, GRID_CRC,
+ GRID_SNAPPY_SMALL, GRID_SNAPPY_LARGE, GRID_SNAPPY_COMP, GRID_COPY_RANGES, GRID_STREAM_COPY, GRID_DECODE_PIPE,
+ GRID_DECODE_TILES) = range(14)
 
 
 class BlockBatch(C.Structure):
@@ -444,6 +449,12 @@ def lib() -> C.CDLL:
         L.mtblx_table_gather.restype = C.c_int
         L.mtblx_dir_ascends.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mtblx_dir_ascends.restype = C.c_int
+        L.mtblx_debug_cu_limit.argtypes = [C.c_int]
+        L.mtblx_debug_cu_limit.restype = C.c_int
+        L.mtblx_debug_grid_items.argtypes = [C.c_int, C.c_int]
+        L.mtblx_debug_grid_items.restype = C.c_uint64
+        L.mtblx_debug_decode_tiles.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_int)]
+        L.mtblx_debug_decode_tiles.restype = C.c_uint32
         L.mtblx_host_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_uint64]
         L.mtblx_host_alloc.restype = C.c_int
         L.mtblx_host_free.argtypes = [C.c_void_p]
